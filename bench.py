@@ -14,6 +14,10 @@ Workloads (--workload, named in config.workload):
 One process per GPU (torchrun); ranks work on independent frame shards (weak scaling, no data-path
 collective); weights are broadcast from rank 0 over RCCL.  `value` = frames of all ranks / max-over-ranks
 wall time of exactly K steps bracketed by barrier + synchronize.
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything measured outside the timed
+steps: stage and per-kernel-family roofline legs, the exact / integer-exact / certified modes, the PCIe legs, the CPU
+baseline with its parity readout and the `secondary` configurations.  --dump-outputs DIR writes what the last timed step
+returned (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -67,7 +71,46 @@ def parse():
     ap.add_argument("--mode", default="replicas", choices=["replicas", "shard"],
                     help="N > 1: independent frame shards per rank (default, no data-path collective) or ONE clip sharded over "
                          "the ranks with the detection / 2D all_gathers of posepipeline_amd/parallel.py")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need (outside the timed region): roofline / stage legs, the other numerics "
+                         "modes, PCIe legs, CPU baseline and parity readout, the `secondary` configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args()
+    if args.dump_outputs and (args.workload not in DUMPABLE or args.mode != "replicas"):
+        ap.error("--dump-outputs: workloads %s in --mode replicas" % ", ".join(DUMPABLE))
+    return args
+
+
+DUMPABLE = ("cascade", "cascade5", "cascade0", "c2", "c5")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _np_out(a):
+    """float32, or float64 where the value has 8-byte elements (int64 indices, float64 coordinates): exact either way"""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a, np.float64 if a.dtype.itemsize == 8 else np.float32)
+
+
+def cascade_outputs(res):
+    """Cascade.step()'s result as flat arrays: the tracker rows of every frame of the chunk, and the 2D / 3D joints decided /
+    emitted in this step, tracks in id order, with (track id, frame) per row in the *_index arrays"""
+    out = {"tracks": np.array([(f, *row[:6]) for f, rows in enumerate(res["tracks"]) for row in rows], np.float64).reshape(-1, 7)}
+    for key in ("keypoints", "keypoints_3d"):
+        tids = sorted(res[key])
+        out[key] = _np_out(np.concatenate([res[key][t] for t in tids]) if tids else np.zeros((0, 0, 3), np.float32))
+        out[key + "_index"] = np.array([(t, f) for t in tids for f in res[key + "_frames"][t]], np.float64).reshape(-1, 2)
+    return out
+
+
+def dump_outputs(d, arrays):
+    arrays = {k: _np_out(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def kernel_source_sha():
@@ -405,6 +448,39 @@ def run_cascade(args, D):
     if D.rank != 0:
         return
     K = args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cascade_outputs(res))
+    flops_step = B * (cas.detector.flops_per_frame + 2 * P * cas.pose_net.prog.flops)
+    out = {
+        "metric": METRIC, "value": D.world * B * K / dt, "unit": "frames/s", "n_gpus": D.world, "steps": K,
+        "warmup": args.warmup, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("f32 (detector, lifting) + bf16 (ViT encoder)" if vit else "f32") +
+                 DTYPE_NOTE + "; `bit_exact_mode` = the same step on the float32 MFMA kernels only",
+        "data": "synthetic",
+        "config": {"workload": ("configs[4]-style cascade on one GPU per rank: 1080p detect (Faster-RCNN R50-FPN) -> SORT -> "
+                                "ViTPose-H 256x192 (bf16 MFMA encoder) flip_test + UDP decode -> VideoPose3D 243-frame lifting") if vit else
+                               ("configs[3] on one GPU per rank: 1080p detect (Faster-RCNN R50-FPN) -> SORT -> HRNet-W48 "
+                                "384x288 flip_test + DARK decode -> VideoPose3D 243-frame lifting"),
+                   "frames_per_step_per_gpu": B, "persons_per_frame": P,
+                   "gflop_per_frame": flops_step / B / 1e9,
+                   "detector_boxes": "detector runs on every frame; downstream boxes are replayed synthetic GT (random-weight detector)",
+                   "contract": "`value` is the FLOAT-TOLERANCE mode (every program on the fp16-form kernels: joints within 1e-3 px / mm on "
+                               "well-conditioned weights, integer outputs NOT guaranteed on near-tie detector decisions); the modes that hold "
+                               "north_star's integer contract are `integer_exact_mode` (detector on the float32 MFMA kernels) and "
+                               "`integer_exact_mode.certified_mode` (fast detector + per-frame decision margins + exact re-runs)",
+                   "detector_lookahead": getattr(cas, "lookahead", "off"),
+                   "host_cores_per_rank": (os.cpu_count() or 1) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", D.world))),
+                   "profile_serial": bool(args.profile_serial)},
+    }
+    if D.world > 1:
+        out["per_rank_ms_per_step"] = per_rank
+        # (replicas: no data-path collective at all -- the only cross-rank traffic of the timed region is the barrier)
+        out["collectives_in_timed_region"] = {"count": 0, "bytes": 0,
+                                               "note": "replicas mode shards FRAMES over ranks with no exchange; --mode shard (one clip over the "
+                                                       "ranks) reports collectives / collective_bytes / collective_wait per rank"}
+    if not args.full:
+        return out
     # stage times: inside the timed region the next chunk's detector pass runs UNDER this chunk's 2D stage, so per-stage event
     # times overlap and sum to more than the step; the breakdown reported is from three extra steps without that overlap
     overlapped = {k: v / K for k, v in stage.items()}
@@ -430,7 +506,6 @@ def run_cascade(args, D):
     for nt in nets:
         nt.set_lanes(True)
     n_launch = len(cas.detector.prog_a.ops) + len(cas.detector.prog_b.ops) + len(cas.pose_net.prog.ops)
-    flops_step = B * (cas.detector.flops_per_frame + 2 * P * cas.pose_net.prog.flops)
     if vit:
         # the fp32 conv roofline covers the detector programs only; the ViT stage is reported beside it (its own roofline
         # line is --workload c5)
@@ -524,38 +599,9 @@ def run_cascade(args, D):
                         "ANY non-bit-identical evaluation in nearly every frame -- the margins say so per frame instead of leaving it to chance"}
             cas_cert.release()
     split_peak_line = BF16_MFMA_PEAK_TFLOPS / fam.get("products", 6)
-    out = {
-        "metric": METRIC, "value": D.world * B * K / dt, "unit": "frames/s", "n_gpus": D.world, "steps": K,
-        "warmup": args.warmup, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("f32 (detector, lifting) + bf16 (ViT encoder)" if vit else "f32") +
-                 DTYPE_NOTE + "; `bit_exact_mode` = the same step on the float32 MFMA kernels only",
-        "data": "synthetic",
-        "config": {"workload": ("configs[4]-style cascade on one GPU per rank: 1080p detect (Faster-RCNN R50-FPN) -> SORT -> "
-                                "ViTPose-H 256x192 (bf16 MFMA encoder) flip_test + UDP decode -> VideoPose3D 243-frame lifting") if vit else
-                               ("configs[3] on one GPU per rank: 1080p detect (Faster-RCNN R50-FPN) -> SORT -> HRNet-W48 "
-                                "384x288 flip_test + DARK decode -> VideoPose3D 243-frame lifting"),
-                   "frames_per_step_per_gpu": B, "persons_per_frame": P,
-                   "gflop_per_frame": flops_step / B / 1e9,
-                   "detector_boxes": "detector runs on every frame; downstream boxes are replayed synthetic GT (random-weight detector)",
-                   "contract": "`value` is the FLOAT-TOLERANCE mode (every program on the fp16-form kernels: joints within 1e-3 px / mm on "
-                               "well-conditioned weights, integer outputs NOT guaranteed on near-tie detector decisions); the modes that hold "
-                               "north_star's integer contract are `integer_exact_mode` (detector on the float32 MFMA kernels) and "
-                               "`integer_exact_mode.certified_mode` (fast detector + per-frame decision margins + exact re-runs)",
-                   "detector_lookahead": getattr(cas, "lookahead", "off"),
-                   "host_cores_per_rank": (os.cpu_count() or 1) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", D.world))),
-                   "profile_serial": bool(args.profile_serial)},
-        "roofline": roof,
-        "bit_exact_mode": exact_mode,
-        "integer_exact_mode": integer_mode if side_legs else None,
-    }
+    out.update({"roofline": roof, "bit_exact_mode": exact_mode, "integer_exact_mode": integer_mode if side_legs else None})
     if D.world > 1:
-        out["per_rank_ms_per_step"] = per_rank
-        # (replicas: no data-path collective at all -- the only cross-rank traffic of the timed region is the barrier)
         out["per_rank_roofline_frac"] = [flops_step / (ms * 1e-3) / 1e12 / split_peak_line for ms in per_rank]
-        out["collectives_in_timed_region"] = {"count": 0, "bytes": 0,
-                                               "note": "replicas mode shards FRAMES over ranks with no exchange; --mode shard (one clip over the "
-                                                       "ranks) reports collectives / collective_bytes / collective_wait per rank"}
     if side_legs:
         # PCIe-inclusive leg (reported beside `value`, never as it): the same chunks streamed from host memory through
         # page-locked staging buffers and the copy stream (posepipeline_amd/streaming.py), upload overlapped with compute
@@ -629,7 +675,7 @@ def secondary_lines(args):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     for key, what, over in legs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--light", "--no-secondary", "--chunk", str(args.chunk)] + over
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--light", "--no-secondary", "--chunk", str(args.chunk)] + over
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
@@ -954,6 +1000,8 @@ def run_c2(args, D):
     dt = D.max_time(time.perf_counter() - t0)
     if D.rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keypoints": kp})
     n_launch = len(prog.ops)
     flops_step = prog.flops * 2 * n
     net_ms = t_net / args.steps
@@ -965,13 +1013,15 @@ def run_c2(args, D):
         "config": {"workload": "configs[1]: HRNet-W32 256x192 top-down 2D, pre-cropped persons, flip_test, decode 'default'",
                    "frames_per_step_per_gpu": n, "backbone_samples_per_step": 2 * n,
                    "not_in_this_line": "detector, tracker, 3D lifting (see --workload cascade)"},
-        "roofline": {**roofline_families(kernel_families([(net, 2 * n)])),
-                     "traffic": pmc_traffic("c2_batch%d" % n)[0],
-                     "program": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
-                                 "avg_launch_ms": net_ms / n_launch,
-                                 "note": "whole backbone program inside the timed region (4 HIP streams): FLOPs / wall time"},
-                     "stage_ms": {"pre": t_pre / args.steps, "backbone": net_ms, "decode": t_dec / args.steps}},
     }
+    if not args.full:
+        return out
+    out["roofline"] = {**roofline_families(kernel_families([(net, 2 * n)])),
+                       "traffic": pmc_traffic("c2_batch%d" % n)[0],
+                       "program": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
+                                   "avg_launch_ms": net_ms / n_launch,
+                                   "note": "whole backbone program inside the timed region (4 HIP streams): FLOPs / wall time"},
+                       "stage_ms": {"pre": t_pre / args.steps, "backbone": net_ms, "decode": t_dec / args.steps}}
     n_cpu = 6 if args.cpu_frames is None else args.cpu_frames
     if n_cpu > 0 and D.world == 1:
         out["cpu_baseline"] = cpu_baseline_c2(sd, x[:n_cpu], cs[:n_cpu], kp[:n_cpu])
@@ -1038,6 +1088,20 @@ def run_c5(args, D):
     dt = D.max_time(time.perf_counter() - t0)
     if D.rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keypoints": kp})
+    out = {
+        "metric": METRIC, "value": D.world * n * args.steps / dt, "unit": "frames/s", "n_gpus": D.world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "configs[4] on one GPU per rank: ViTPose-H 256x192 top-down 2D, pre-cropped persons, flip_test, "
+                               "UDP decode (bf16 MFMA encoder, fp32 patch embedding and deconvolution head)",
+                   "frames_per_step_per_gpu": n, "backbone_samples_per_step": 2 * n,
+                   "gflop_per_frame": prog.flops * 2 / 1e9,
+                   "not_in_this_line": "detector, tracker, 3D lifting (see --workload cascade); ViTPose is not in the reference tree"},
+    }
+    if not args.full:
+        return out
     # roofline leg (outside the timed region): HIP events after every encoder launch, summed per kernel family
     ms3 = np.zeros(3, np.float32)
     n_gemm = ctypes.c_int(0)
@@ -1048,23 +1112,13 @@ def run_c5(args, D):
     gemm_flops = 2.0 * m_rows * (4 * d * d + 2 * d * hid) * spec.depth
     achieved = gemm_flops / (float(ms3[0]) * 1e-3) / 1e12
     net_ms = t_net / args.steps
-    out = {
-        "metric": METRIC, "value": D.world * n * args.steps / dt, "unit": "frames/s", "n_gpus": D.world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": "configs[4] on one GPU per rank: ViTPose-H 256x192 top-down 2D, pre-cropped persons, flip_test, "
-                               "UDP decode (bf16 MFMA encoder, fp32 patch embedding and deconvolution head)",
-                   "frames_per_step_per_gpu": n, "backbone_samples_per_step": 2 * n,
-                   "gflop_per_frame": prog.flops * 2 / 1e9,
-                   "not_in_this_line": "detector, tracker, 3D lifting (see --workload cascade); ViTPose is not in the reference tree"},
-        "roofline": {"bound": "mfma", "kernel": "gemm_bf16_kernel (%d launches per step: qkv / proj / fc1 / fc2 of %d blocks)" % (n_gemm.value, spec.depth),
-                     "achieved": achieved, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / BF16_MFMA_PEAK_TFLOPS,
-                     "traffic": pmc_traffic("c5_batch%d" % n)[0], "flops_per_launch": gemm_flops / max(n_gemm.value, 1),
-                     "avg_launch_ms": float(ms3[0]) / max(n_gemm.value, 1),
-                     "encoder_ms": {"gemm": float(ms3[0]), "layernorm": float(ms3[1]), "attention": float(ms3[2])},
-                     "program_tflops": prog.flops * 2 * n / (net_ms * 1e-3) / 1e12,
-                     "stage_ms": {"pre": t_pre / args.steps, "backbone": net_ms, "decode": t_dec / args.steps}},
-    }
+    out["roofline"] = {"bound": "mfma", "kernel": "gemm_bf16_kernel (%d launches per step: qkv / proj / fc1 / fc2 of %d blocks)" % (n_gemm.value, spec.depth),
+                       "achieved": achieved, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / BF16_MFMA_PEAK_TFLOPS,
+                       "traffic": pmc_traffic("c5_batch%d" % n)[0], "flops_per_launch": gemm_flops / max(n_gemm.value, 1),
+                       "avg_launch_ms": float(ms3[0]) / max(n_gemm.value, 1),
+                       "encoder_ms": {"gemm": float(ms3[0]), "layernorm": float(ms3[1]), "attention": float(ms3[2])},
+                       "program_tflops": prog.flops * 2 * n / (net_ms * 1e-3) / 1e12,
+                       "stage_ms": {"pre": t_pre / args.steps, "backbone": net_ms, "decode": t_dec / args.steps}}
     n_cpu = 1 if args.cpu_frames is None else args.cpu_frames
     if n_cpu > 0 and D.world == 1:
         hm_gpu = net.read("output", 2 * n).reshape(2 * n, 17, *spec.heatmap_hw)
@@ -1158,7 +1212,7 @@ def run_track0(args, D):
     flops_step = det.prog.flops * B
     achieved = flops_step / (net_ms * 1e-3) / 1e12
     n_launch = sum(1 for op in det.prog.ops if op.type == 1)
-    return {
+    out = {
         "metric": "frames/sec, DeepSortYOLOv4 tracking stage on 1080p (not the headline metric)",
         "value": D.world * B * args.steps / dt, "unit": "frames/s", "n_gpus": D.world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -1166,13 +1220,16 @@ def run_track0(args, D):
         "config": {"workload": "tracking_method 0: letterbox -> YOLOv4 416 -> decode/NMS -> mars-small128 -> DeepSORT",
                    "frames_per_step_per_gpu": B, "persons_per_frame": args.persons, "tracks_per_step": n_trk,
                    "detector_boxes": "detector + decode + NMS run on every frame; downstream boxes are replayed synthetic persons"},
-        # per kernel family, live (HIP events around every launch of one serial pass): YOLOv4's 3x3 / wide 1x1 layers run on the
-        # split kernels since round 2, so the dominant family and ITS peak are reported, not the fp32 kernels' 157.3
-        "roofline": {**roofline_families(kernel_families([(det.net, B)])), "traffic": None,
-                     "program": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
-                                 "avg_launch_ms": net_ms / n_launch,
-                                 "note": "YOLOv4 program inside the timed region (Mish epilogues in fp64): FLOPs / wall time"}},
     }
+    if not args.full:
+        return out
+    # per kernel family, live (HIP events around every launch of one serial pass): YOLOv4's 3x3 / wide 1x1 layers run on the
+    # split kernels since round 2, so the dominant family and ITS peak are reported, not the fp32 kernels' 157.3
+    out["roofline"] = {**roofline_families(kernel_families([(det.net, B)])), "traffic": None,
+                       "program": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
+                                   "avg_launch_ms": net_ms / n_launch,
+                                   "note": "YOLOv4 program inside the timed region (Mish epilogues in fp64): FLOPs / wall time"}}
+    return out
 
 
 def run_cascade0(args, D):
@@ -1215,12 +1272,14 @@ def run_cascade0(args, D):
     dt = D.max_time(time.perf_counter() - t0)
     if D.rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cascade_outputs(res))
     K = args.steps
     conv_ms = (st["yolo"] + st["pose"]) / K
     flops_step = B * (cas.detector.flops_per_frame + 2 * P * cas.pose_net.prog.flops)
     n_launch = len(cas.detector.prog.ops) + len(cas.pose_net.prog.ops)
     achieved = flops_step / (conv_ms * 1e-3) / 1e12
-    return {
+    out = {
         "metric": METRIC, "value": D.world * B * K / dt, "unit": "frames/s", "n_gpus": D.world, "steps": K, "warmup": args.warmup,
         "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
         "data": "synthetic",
@@ -1229,12 +1288,15 @@ def run_cascade0(args, D):
                    "frames_per_step_per_gpu": B, "persons_per_frame": P, "gflop_per_frame": flops_step / B / 1e9,
                    "tracks_in_last_frame": len(res["tracks"][-1]),
                    "detector_boxes": "detector + decode + NMS run on every frame; downstream boxes are replayed synthetic GT (random-weight detector)"},
-        "roofline": {**roofline_families(kernel_families([(cas.detector.net, B), (cas.pose_net, 2 * B * P)])), "traffic": None,
-                     "programs": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
-                                  "avg_launch_ms": conv_ms / n_launch,
-                                  "note": "YOLOv4 + HRNet-W48 programs inside the timed region: FLOPs / wall time"},
-                     "stage_ms": {"yolo_backbone": st["yolo"] / K, "pose_backbone": st["pose"] / K}},
     }
+    if not args.full:
+        return out
+    out["roofline"] = {**roofline_families(kernel_families([(cas.detector.net, B), (cas.pose_net, 2 * B * P)])), "traffic": None,
+                       "programs": {"achieved": achieved, "launches": n_launch, "flops_per_launch": flops_step / n_launch,
+                                    "avg_launch_ms": conv_ms / n_launch,
+                                    "note": "YOLOv4 + HRNet-W48 programs inside the timed region: FLOPs / wall time"},
+                       "stage_ms": {"yolo_backbone": st["yolo"] / K, "pose_backbone": st["pose"] / K}}
+    return out
 
 
 def run_plumbing(args, D):

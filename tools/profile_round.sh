@@ -5,15 +5,15 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/bench_cascade.json 2> $O/bench_cascade.err
-python $R/bench.py --workload c2 > $O/bench_c2.json 2> $O/bench_c2.err
-python $R/bench.py --mode shard --steps 6 --warmup 2 > $O/bench_shard.json 2> $O/bench_shard.err
-python $R/bench.py --persons 4 --steps 6 --warmup 2 --cpu-frames 0 > $O/bench_cascade_p4.json 2> $O/bench_cascade_p4.err
-python $R/bench.py --persons 8 --steps 4 --warmup 1 --cpu-frames 0 --no-secondary > $O/bench_cascade_p8.json 2> $O/bench_cascade_p8.err
+python $R/bench.py --full > $O/bench_cascade.json 2> $O/bench_cascade.err
+python $R/bench.py --full --workload c2 > $O/bench_c2.json 2> $O/bench_c2.err
+python $R/bench.py --full --mode shard --steps 6 --warmup 2 > $O/bench_shard.json 2> $O/bench_shard.err
+python $R/bench.py --full --persons 4 --steps 6 --warmup 2 --cpu-frames 0 > $O/bench_cascade_p4.json 2> $O/bench_cascade_p4.err
+python $R/bench.py --full --persons 8 --steps 4 --warmup 1 --cpu-frames 0 --no-secondary > $O/bench_cascade_p8.json 2> $O/bench_cascade_p8.err
 cd $R
 # the roofline evidence: ONE run under rocprofv3 with every launch on one stream and no detector look-ahead (--profile-serial), so that
 # AverageNs of conv_split_* x launches_per_step reproduces the line's ms_per_step_serial (tools/roofline_check.py prints both)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python bench.py --profile-serial --steps 5 --warmup 1 > $O/serial.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python bench.py --full --profile-serial --steps 5 --warmup 1 > $O/serial.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/lanes4 -- python bench.py --steps 5 --warmup 1 --cpu-frames 0 > $O/lanes4.log 2>&1
 cp $(ls -t $(find $O/serial -name "*kernel_stats.csv") | head -1) $O/cascade_serial_kernel_stats.csv
 cp $(ls -t $(find $O/lanes4 -name "*kernel_stats.csv") | head -1) $O/cascade_lanes_kernel_stats.csv
@@ -43,8 +43,8 @@ DECODE_ONE=64 bash tools/hbm_kernel_profile.sh flip_merge_decode decode_n64 6016
 DECODE_ONE=256 bash tools/hbm_kernel_profile.sh flip_merge_decode decode_n256 240648192 python tools/hbm_kernels_bench.py decode > /dev/null 2>&1; cp gpurun_out/hbm_decode_n256.txt $O/hbm_decode_n256.txt
 NV12_ONE=1 bash tools/hbm_kernel_profile.sh nv12_to_bgr nv12_1080p 597196800 python tools/hbm_kernels_bench.py nv12 > /dev/null 2>&1; cp gpurun_out/hbm_nv12_1080p.txt $O/hbm_nv12_1080p.txt
 bash tools/hbm_kernel_profile.sh det_preprocess det_preprocess 1111228416 python bench.py --steps 3 --warmup 1 --light --cpu-frames 0 > /dev/null 2>&1; cp gpurun_out/hbm_det_preprocess.txt $O/hbm_det_preprocess.txt
-python bench.py --workload c5 --cpu-frames 0 > $O/bench_c5.json 2> $O/bench_c5.err
-python bench.py --workload cascade5 --cpu-frames 0 --steps 6 --warmup 2 > $O/bench_cascade5.json 2> $O/bench_cascade5.err
+python bench.py --full --workload c5 --cpu-frames 0 > $O/bench_c5.json 2> $O/bench_c5.err
+python bench.py --full --workload cascade5 --cpu-frames 0 --steps 6 --warmup 2 > $O/bench_cascade5.json 2> $O/bench_cascade5.err
 python tools/margin_probe.py 16 > $O/margin_probe.txt 2>&1
 bash tools/pmc_kernel.sh "conv_split_kernel<9, 6, 4, 2, 4, true, true, false>" tap4 python tools/profile_net.py det 64 > /dev/null 2>&1; cp gpurun_out/pmc_tap4/summary.txt $O/tap_kernel_pmc.txt
 bash tools/pmc_kernel.sh "true, true, true>" s2p python tools/profile_net.py det 64 > /dev/null 2>&1; cp gpurun_out/pmc_s2p/summary.txt $O/s2_kernel_pmc.txt

@@ -2,7 +2,7 @@
 """Recompute bench.py's `roofline` from a rocprofv3 --kernel-trace --stats summary of the SAME run.
 
 usage: python tools/roofline_check.py <kernel_stats.csv> <bench line .json>
-The run must be `python bench.py --profile-serial ...` (every launch on one stream, no detector look-ahead): per-kernel
+The run must be `python bench.py --full --profile-serial ...` (every launch on one stream, no detector look-ahead): per-kernel
 durations are additive only then.  For the kernel family the line names (`conv_split_*` or the float32 MFMA kernels):
 launches, total and average duration from the CSV; average x launches_per_step against the line's ms_per_step_serial
 (HIP events inside bench.py); the roofline fraction recomputed from the CSV."""
