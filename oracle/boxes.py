@@ -3,6 +3,10 @@
   * nms_deepsort: greedy NMS of pose_pipeline/wrappers/deep_sort_yolov4/deep_sort/preprocessing.py:5-70
     (tlwh boxes, +1 pixel areas :47, overlap = intersection / area of the OTHER box :66, suppress
     overlap > thr, picks in descending score order).  Pinned by tests/golden/nms_deepsort.npz.
+  * nms_deepsort_stable: the same NMS read with a STABLE ascending argsort, so that among equal scores the
+    higher index is popped first.  numpy's default argsort (what nms_deepsort keeps, as the reference wrote
+    it) is only stable for small n on SIMD builds, so the reference's own tie order is platform-defined for
+    large n; this reading is the contract the device kernel (nms.hip, convention 1) keeps.
   * nms_mmcv: the detector-side convention (mmcv-full `nms` / torchvision: x1y1x2y2, area = w*h, IoU,
     suppress IoU > thr, stable descending score order) selected by
     3rdparty/mmtracking/_base_/models/faster_rcnn_r50_fpn.py:101-109.  mmcv is not vendored: restated
@@ -35,6 +39,27 @@ def nms_deepsort(boxes_tlwh, max_overlap, scores=None):
             if (w * h) / area[j] <= max_overlap:
                 keep.append(j)
         idxs = keep
+    return pick
+
+
+def nms_deepsort_stable(boxes_tlwh, max_overlap, scores):
+    """nms_deepsort with scores, vectorised, sorted by np.argsort(scores, kind="stable") and popped from the end."""
+    boxes = np.asarray(boxes_tlwh, dtype=np.float64).reshape(-1, 4)
+    order = np.argsort(np.asarray(scores, np.float64).reshape(-1), kind="stable")[::-1]
+    b = boxes[order]
+    x1, y1 = b[:, 0], b[:, 1]
+    x2, y2 = b[:, 2] + b[:, 0], b[:, 3] + b[:, 1]
+    area = (x2 - x1 + 1) * (y2 - y1 + 1)
+    suppressed = np.zeros(len(b), bool)
+    pick = []
+    for i in range(len(b)):
+        if suppressed[i]:
+            continue
+        pick.append(int(order[i]))
+        r = slice(i + 1, len(b))
+        w = np.maximum(0.0, np.minimum(x2[i], x2[r]) - np.maximum(x1[i], x1[r]) + 1)
+        h = np.maximum(0.0, np.minimum(y2[i], y2[r]) - np.maximum(y1[i], y1[r]) + 1)
+        suppressed[r] |= ~((w * h) / area[r] <= max_overlap)
     return pick
 
 

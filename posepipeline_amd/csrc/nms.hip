@@ -8,7 +8,11 @@
 //   (ties: lower index first).
 // convention 1 -- the in-tree greedy NMS, wrappers/deep_sort_yolov4/deep_sort/preprocessing.py:5-70:
 //   float64 (x, y, w, h) boxes, +1-pixel areas (:47), overlap = intersection / area of the OTHER box (:66),
-//   suppress overlap > thr, survivors in descending score order.
+//   suppress overlap > thr, survivors in descending score order (ties: HIGHER index first).  The reference sorts
+//   with an ascending np.argsort and pops from the end, so among equal scores the stable reading of that
+//   argsort emits the higher index first.  numpy's default argsort is only stable for a handful of elements
+//   on SIMD builds (numpy 2.x with AVX-512), so the reference's own tie order is platform-defined beyond
+//   that; the stable reading is the contract.
 // convention 2 -- tf.image.non_max_suppression as called by wrappers/deep_sort_yolov4/yolo4/model.py:278-281:
 //   float32 (y1, x1, y2, x2) with corners in any order, IoU = inter / (Sa + Sb - inter) (0 when an area is <= 0),
 //   suppress IoU > thr, survivors in descending score order (ties: lower index first); the caller truncates to
@@ -20,7 +24,8 @@ namespace {
 
 constexpr int MAX_N = 8192;
 
-template <typename T>
+// TIE_HIGH: equal scores go higher index first (convention 1); otherwise lower index first
+template <typename T, bool TIE_HIGH>
 __global__ __launch_bounds__(1024) void sort_desc_kernel(const T* __restrict__ scores, const int32_t* __restrict__ n_ptr,
                                                          int max_n, int32_t* __restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -33,10 +38,10 @@ __global__ __launch_bounds__(1024) void sort_desc_kernel(const T* __restrict__ s
     const T* sc = scores + (size_t)f * max_n;
     for (int i = threadIdx.x; i < npow2; i += blockDim.x) {
         key[i] = i < n ? sc[i] : (T)-INFINITY;
-        idx[i] = i < n ? i : 0x7fffffff;
+        idx[i] = i < n ? i : (TIE_HIGH ? -1 : 0x7fffffff);     // padding sorts after every real box, -inf scores included
     }
     __syncthreads();
-    // bitonic sort; "a before b" <=> key_a > key_b || (key_a == key_b && idx_a < idx_b)
+    // bitonic sort; "a before b" <=> key_a > key_b || (key_a == key_b && (TIE_HIGH ? idx_a > idx_b : idx_a < idx_b))
     for (int k = 2; k <= npow2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = threadIdx.x; i < npow2; i += blockDim.x) {
@@ -45,7 +50,7 @@ __global__ __launch_bounds__(1024) void sort_desc_kernel(const T* __restrict__ s
                     const bool up = (i & k) == 0;
                     const T ka = key[i], kb = key[l];
                     const int ia = idx[i], ib = idx[l];
-                    const bool a_first = ka > kb || (ka == kb && ia < ib);
+                    const bool a_first = ka > kb || (ka == kb && (TIE_HIGH ? ia > ib : ia < ib));
                     if (a_first != up) {
                         key[i] = kb; key[l] = ka;
                         idx[i] = ib; idx[l] = ia;
@@ -275,8 +280,8 @@ int run_nms(hipStream_t s, const T* d_boxes, const T* d_scores, const int32_t* d
             int32_t* d_order, unsigned long long* d_mask, int32_t* d_keep, int32_t* d_nkeep, unsigned char* d_kflag = nullptr) {
     const size_t lds = (size_t)MAX_N * (sizeof(T) + sizeof(int32_t));
     static PpPerDeviceOnce attr_set;
-    attr_set.run([&] { (void)hipFuncSetAttribute((const void*)sort_desc_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    hipLaunchKernelGGL((sort_desc_kernel<T>), dim3(n_frames), dim3(1024), lds, s, d_scores, d_n, max_n, d_order);
+    attr_set.run([&] { (void)hipFuncSetAttribute((const void*)sort_desc_kernel<T, CONV == 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    hipLaunchKernelGGL((sort_desc_kernel<T, CONV == 1>), dim3(n_frames), dim3(1024), lds, s, d_scores, d_n, max_n, d_order);
     const int words = (max_n + 63) / 64;
     hipLaunchKernelGGL((nms_mask_kernel<T, CONV>), dim3(words, words, n_frames), dim3(64), 0, s, d_boxes, d_order, d_n, max_n,
                        thr, d_mask, words);

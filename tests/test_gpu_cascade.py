@@ -271,6 +271,41 @@ def test_cascade_with_default_tracking_method(ctx):
     assert np.array_equal(out[2]["keypoints_3d"][tid], reference_3d(k2, 0, 4, w, h, lift_sd))
 
 
+def test_deepsort_cascade_equal_confidences_take_the_reference_id_order(ctx):
+    """Two people appear in the first frame with equal confidence and boxes that do not overlap, and stay apart.  parser.py passes
+    the NMS keep list (nms_max_overlap 1.0: nothing is suppressed, the ORDER is the whole output) straight to DeepSORT, which starts
+    tracks in that order.  The reference's NMS sorts with an ascending argsort and pops from the end, so the person at the HIGHER
+    replay index comes out first and gets track id 1 (oracle.boxes.nms_deepsort on these two boxes)."""
+    from oracle import boxes as obox
+    from posepipeline_amd.cascade import Cascade
+    from posepipeline_amd.models import mars, yolov4
+    rng = np.random.default_rng(12)
+    h, w, n = 135, 240, 4
+    frames = np.stack([synth_frame(rng, h, w) for _ in range(n)])
+    ysd = yolov4.synth_params(yolov4.yolov4_param_shapes(), seed=4, head_bias=-2.0)
+    msd = yolov4.synth_params(mars.mars_param_shapes(), seed=5)
+    pose_spec = hrnet.HRNetSpec(32, 17, 128, 96)
+    pose_sd = synth.synth_state_dict(hrnet.hrnet_param_shapes(pose_spec), seed=1)
+    lift_sd = synth.synth_state_dict(vp3d.videopose3d_param_shapes(vp3d.VideoPose3DSpec()), seed=3)
+    cas = Cascade(ctx, (ysd, msd), pose_sd, lift_sd, h, w, chunk=2, max_persons=2, pose_spec=pose_spec, tracking="DeepSortYOLOv4")
+    # replay index 0: person A on the left, index 1: person B on the right, both at confidence 0.9 (a saturated YOLO score ties the
+    # same way); 2 px a frame, 80 px apart
+    gt = [np.array([[20 + 2 * t, 20, 80 + 2 * t, 120, 0.9], [160 - 2 * t, 15, 220 - 2 * t, 115, 0.9]], np.float32) for t in range(n)]
+    first = np.array([[20, 20, 60, 100], [160, 15, 60, 100]], np.float64)
+    assert obox.nms_deepsort(first, 1.0, np.array([0.9, 0.9])) == [1, 0]        # the reference: B first
+    out = [cas.step(frames[0:2], replay=gt[0:2]), cas.step(frames[2:4], replay=gt[2:4]), cas.flush()]
+    tracks = [t for o in out for t in o["tracks"]]
+    assert len(tracks) == n
+    for t, rows in enumerate(tracks):
+        by_id = {r[0]: np.asarray(r[6], np.float64) for r in rows}
+        assert sorted(by_id) == [1, 2], (t, sorted(by_id))
+        ctr = {i: b[:2] + b[2:] / 2 for i, b in by_id.items()}
+        a_ctr, b_ctr = np.array([50 + 2 * t, 70]), np.array([190 - 2 * t, 65])
+        assert np.abs(ctr[1] - b_ctr).max() < 10 and np.abs(ctr[2] - a_ctr).max() < 10, (t, ctr)     # id 1 = B, id 2 = A
+        if t == 0:     # the Kalman mean starts at the detection: the track box is the (int-truncated) input box
+            assert np.allclose(by_id[1], first[1]) and np.allclose(by_id[2], first[0])
+
+
 def test_cascade_steady_state_keeps_device_memory_flat(ctx):
     """A long-running cascade (tracks born and lost all the time: every 96 frames the person jumps to another place, so a new id
     and a new person stream replace the old ones) must not grow: device memory in use after 12 chunks equals the level after 4

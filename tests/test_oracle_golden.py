@@ -85,6 +85,25 @@ def test_nms_deepsort_oracle():
         assert pick == g[f"n{k}_pick"].tolist(), f"case {k}"
 
 
+def test_nms_deepsort_stable_reading_matches_goldens():
+    """The stable reading of the reference's argsort (ties: higher index first), which nms.hip convention 1 keeps, reproduces
+    every recorded score-ordered pick, the twelve cases with tied scores included -- and in five of them the recorded pick
+    holds the tied indices 5 and 3 in that order, so the lower-index-first order would not."""
+    g = load("nms_deepsort.npz")
+    checked = ties = both = 0
+    for k in range(int(g["n_cases"])):
+        if not bool(g[f"n{k}_use_scores"]):
+            continue
+        scores, pick = g[f"n{k}_scores"], g[f"n{k}_pick"].tolist()
+        assert obox.nms_deepsort_stable(g[f"n{k}_boxes"], float(g[f"n{k}_thr"]), scores) == pick, f"case {k}"
+        checked += 1
+        if len(np.unique(scores)) != len(scores):
+            ties += 1
+            assert scores[3] == scores[5]
+            both += 5 in pick and 3 in pick and pick.index(5) < pick.index(3)
+    assert (checked, ties, both) == (20, 12, 5)
+
+
 # ---- PersonBbox.make ------------------------------------------------------------------------------------
 def test_person_bbox_selection_and_smoothing():
     g = load("person_bbox.npz")
