@@ -264,7 +264,7 @@ struct pp_net {
     size_t n_weights = 0;
     // conv_split.hip: the eligible convs' weights as bf16 planes in fragment order (built on the device at creation)
     unsigned char* wsplit = nullptr;
-    std::vector<long long> wsplit_off;   // per op: byte offset into wsplit, -1: the op runs on the fp32-MFMA kernels
+    std::vector<SplitPlan> split_plan;   // per op, split nets: how the op runs on the split kernels (SPLIT_NONE: the fp32-MFMA kernels)
     int numerics = PP_NET_NUMERICS_EXACT;   // fixed at creation (ABI 7)
     int split_f16 = 0;                      // split nets: the fp16 form (ABI 9), fixed at creation as well
     // fp16 form (pp_amax.h): per-sample running maxima of the tensors its convolutions read, [slot][max_batch] bit patterns.  A slot
@@ -313,7 +313,7 @@ static void net_plan_amax(pp_net* net) {
     net->slot_owner.clear();
     net->ext.clear();
     if (net->numerics != PP_NET_NUMERICS_SPLIT || !net->split_f16) return;
-    auto is_h = [&](int i) { return net->ops[i].type == PP_OP_CONV && net->wsplit_off[i] >= 0; };
+    auto is_h = [&](int i) { return net->ops[i].type == PP_OP_CONV && net->split_plan[i].kernel != SPLIT_NONE; };
     // producers with a fused maximum: convolutions (pp_conv_tracks_amax) and PP_OP_UPSAMPLE_ADD
     auto tracks = [&](int i) {
         const pp_op& op = net->ops[i];
@@ -585,7 +585,7 @@ static ConvArgs net_conv_args(pp_net* net, const pp_op& op, int batch) {
     a.r1_pad = op.res1 >= 0 ? net->bufs[op.res1].pad : 0;
     a.r2_pad = op.res2 >= 0 ? net->bufs[op.res2].pad : 0;
     const size_t idx = &op - net->ops.data();
-    a.wsplit = (net->wsplit && idx < net->wsplit_off.size() && net->wsplit_off[idx] >= 0) ? net->wsplit + net->wsplit_off[idx] : nullptr;
+    a.wsplit = (net->wsplit && idx < net->split_plan.size() && net->split_plan[idx].off >= 0) ? net->wsplit + net->split_plan[idx].off : nullptr;
     a.numerics = net->numerics;
     a.split_f16 = net->split_f16;
     if (idx < net->op_x_slot.size()) {
@@ -610,7 +610,7 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
     const pp_buf& bo = net->bufs[op.out];
     if (op.type == PP_OP_CONV) {
         const ConvArgs a = net_conv_args(net, op, batch);
-        return pp_launch_conv(a, s);
+        return pp_launch_conv(a, &net->split_plan[&op - net->ops.data()], s);
     } else if (op.type == PP_OP_MAXPOOL) {
         PoolArgs p{};
         p.x = net->buf_ptr(op.in); p.y = net->buf_ptr(op.out);
@@ -736,16 +736,17 @@ int pp_net_create_ex(pp_ctx* ctx, const pp_op* ops, int n_ops, const pp_buf* buf
             return rc;
         }
     }
-    // bf16-split copies of the weights of every conv the split kernel will run
-    net->wsplit_off.assign(n_ops, -1);
+    // each conv op's split kernel, planned once, and the bf16-split copies of the weights of every conv it will run
+    net->split_plan.assign(n_ops, SplitPlan());
     if (net->numerics == PP_NET_NUMERICS_SPLIT) {
         size_t bytes = 0;
         for (int i = 0; i < n_ops; ++i) {
             if (net->ops[i].type != PP_OP_CONV) continue;
-            const ConvArgs a = net_conv_args(net.get(), net->ops[i], 1);
-            if (!pp_conv_split_eligible(a)) continue;
-            net->wsplit_off[i] = (long long)bytes;
-            bytes += (pp_conv_split_bytes(a) + 255) / 256 * 256;
+            SplitPlan p = pp_conv_split_plan(net_conv_args(net.get(), net->ops[i], 1));
+            if (p.kernel == SPLIT_NONE) continue;
+            p.off = (long long)bytes;
+            bytes += (p.bytes + 255) / 256 * 256;
+            net->split_plan[i] = p;
         }
         net_plan_amax(net.get());
         if (!net->slot_owner.empty()) {
@@ -756,9 +757,9 @@ int pp_net_create_ex(pp_ctx* ctx, const pp_op* ops, int n_ops, const pp_buf* buf
         if (bytes) {
             PP_HIP_CHECK(hipMalloc((void**)&net->wsplit, bytes));
             for (int i = 0; i < n_ops; ++i) {
-                if (net->wsplit_off[i] < 0) continue;
-                const ConvArgs a = net_conv_args(net.get(), net->ops[i], 1);
-                int rc = pp_conv_split_weights(a, net->wsplit + net->wsplit_off[i], ctx->stream);
+                const SplitPlan& p = net->split_plan[i];
+                if (p.kernel == SPLIT_NONE) continue;
+                int rc = pp_conv_split_weights(p, net_conv_args(net.get(), net->ops[i], 1), net->wsplit + p.off, ctx->stream);
                 if (rc != PP_OK) return rc;
             }
         }
@@ -824,7 +825,7 @@ int pp_net_conv_kinds(pp_net* net, int* kinds) {
             kinds[i] = 0;
             continue;
         }
-        kinds[i] = (net->numerics == PP_NET_NUMERICS_SPLIT && net->wsplit && net->wsplit_off[i] >= 0) ? 2 : 1;
+        kinds[i] = net->split_plan[i].kernel != SPLIT_NONE ? 2 : 1;
     }
     return PP_OK;
 }
@@ -1034,7 +1035,7 @@ int pp_conv2d(pp_ctx* ctx, const pp_op* op, int n, int hin, int win, const float
     const size_t r2_e = res2 ? y_e : 0;
     if (mem == PP_MEM_DEVICE) {
         a.x = x; a.w = w; a.bias = bias; a.res1 = res1; a.res2 = res2; a.y = y;
-        return pp_launch_conv(a, ctx->stream);
+        return pp_launch_conv(a, nullptr, ctx->stream);
     }
     size_t total = 0;
     for (size_t e : {x_e, w_e, b_e, y_e, r1_e, r2_e}) total += ScratchCursor::align(e * sizeof(float));
@@ -1054,7 +1055,7 @@ int pp_conv2d(pp_ctx* ctx, const pp_op* op, int n, int hin, int win, const float
     if (res1) PP_HIP_CHECK(hipMemcpyAsync(dr1, res1, r1_e * 4, hipMemcpyHostToDevice, s));
     if (res2) PP_HIP_CHECK(hipMemcpyAsync(dr2, res2, r2_e * 4, hipMemcpyHostToDevice, s));
     a.x = dx; a.w = dw; a.bias = db; a.res1 = res1 ? dr1 : nullptr; a.res2 = res2 ? dr2 : nullptr; a.y = dy;
-    rc = pp_launch_conv(a, s);
+    rc = pp_launch_conv(a, nullptr, s);
     if (rc != PP_OK) return rc;
     PP_HIP_CHECK(hipMemcpyAsync(y, dy, y_e * 4, hipMemcpyDeviceToHost, s));
     PP_HIP_CHECK(hipStreamSynchronize(s));

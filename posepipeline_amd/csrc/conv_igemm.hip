@@ -700,7 +700,7 @@ int pp_conv_prepare(const ConvArgs& a) {
     return tap_table_for(a, true) ? PP_OK : PP_ERR_HIP;
 }
 
-int pp_launch_conv(const ConvArgs& a_in, hipStream_t stream) {
+int pp_launch_conv(const ConvArgs& a_in, const SplitPlan* plan, hipStream_t stream) {
     ConvArgs a = a_in;
     a.tap_table = nullptr;
     magic_u32((unsigned)a.HWout, &a.div_hw_m, &a.div_hw_s1, &a.div_hw_s2);
@@ -742,34 +742,36 @@ int pp_launch_conv(const ConvArgs& a_in, hipStream_t stream) {
             if (a.res2) p.res2 = a.res2 + (size_t)n0 * r2_img;
             if (a.x_amax) p.x_amax = a.x_amax + n0;
             if (a.y_amax) p.y_amax = a.y_amax + n0;
-            const int rc = pp_launch_conv(p, stream);
+            const int rc = pp_launch_conv(p, plan, stream);
             if (rc != PP_OK) return rc;
         }
         return PP_OK;
     }
     a.x_bytes = (unsigned)((size_t)a.N * img_bytes);
     if (a.y_stride == 0) a.y_stride = a.Cout;
-    // an op of a net: the split kernel exactly where the net built split weights at creation (nothing is decided at launch time);
-    // single-op API (numerics 0): the process-wide setting, with a temporary split copy of the weights
-    if (a.numerics == PP_NET_NUMERICS_SPLIT && a.wsplit) return pp_launch_conv_split(a, stream);
-    if (a.numerics == 0 && pp_conv_split_enabled() && pp_conv_split_eligible(a)) {
-        if (a.wsplit) return pp_launch_conv_split(a, stream);
+    // an op of a net: the split kernel exactly where the net planned it at creation, with the split weights built for that plan;
+    // single-op API (numerics 0): the process-wide setting, planned for this call, with a temporary split copy of the weights
+    if (plan && plan->kernel != SPLIT_NONE) return pp_launch_conv_split(*plan, a, stream);
+    if (!plan && a.numerics == 0 && pp_conv_split_enabled()) {
         a.split_f16 = pp_conv_split_f16_default();
-        void* tmp = nullptr;                 // single-op API: split the weights for this call
-        const size_t wbytes = (pp_conv_split_bytes(a) + 255) / 256 * 256;
-        PP_HIP_CHECK(hipMalloc(&tmp, wbytes + (a.split_f16 ? (size_t)a.N * sizeof(unsigned) : 0)));
-        a.wsplit = tmp;
-        int rc = pp_conv_split_weights(a, tmp, stream);
-        if (rc == PP_OK && a.split_f16) {    // ... and take the per-sample maxima of the input (a net tracks them where the tensor is produced)
-            unsigned* am = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(tmp) + wbytes);
-            if (hipMemsetAsync(am, 0, (size_t)a.N * sizeof(unsigned), stream) != hipSuccess) rc = PP_ERR_HIP;
-            if (rc == PP_OK) rc = pp_launch_amax(a.x, a.N, img_bytes / sizeof(float), am, stream);
-            a.x_amax = am;
+        const SplitPlan p = pp_conv_split_plan(a);
+        if (p.kernel != SPLIT_NONE) {
+            void* tmp = nullptr;
+            const size_t wbytes = (p.bytes + 255) / 256 * 256;
+            PP_HIP_CHECK(hipMalloc(&tmp, wbytes + (p.f16 ? (size_t)a.N * sizeof(unsigned) : 0)));
+            a.wsplit = tmp;
+            int rc = pp_conv_split_weights(p, a, tmp, stream);
+            if (rc == PP_OK && p.f16) {      // ... and take the per-sample maxima of the input (a net tracks them where the tensor is produced)
+                unsigned* am = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(tmp) + wbytes);
+                if (hipMemsetAsync(am, 0, (size_t)a.N * sizeof(unsigned), stream) != hipSuccess) rc = PP_ERR_HIP;
+                if (rc == PP_OK) rc = pp_launch_amax(a.x, a.N, img_bytes / sizeof(float), am, stream);
+                a.x_amax = am;
+            }
+            if (rc == PP_OK) rc = pp_launch_conv_split(p, a, stream);
+            (void)hipStreamSynchronize(stream);
+            (void)hipFree(tmp);
+            return rc;
         }
-        if (rc == PP_OK) rc = pp_launch_conv_split(a, stream);
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(tmp);
-        return rc;
     }
     if (a.y_amax && !pp_conv_tracks_amax(a, false)) {
         pp_set_error("conv: this layer's epilogue does not track the output maximum (ConvArgs::y_amax; see pp_conv_tracks_amax)");

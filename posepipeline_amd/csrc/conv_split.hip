@@ -1973,11 +1973,6 @@ int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
-struct TileGeom {
-    int TH, TW, bw_log2, gx_log2, PWp, NP, NPp, tiles_x, tiles_y;
-    double eff;
-};
-
 // the 256-pixel tile shape (8 blocks of 32 pixels) that wastes the fewest pixels on this map
 TileGeom pick_tile(int H, int W, int max_np, int pxb) {
     static const int force = env_int("POSEPIPE_SPLIT_TILE", -1);
@@ -2260,26 +2255,55 @@ __global__ __launch_bounds__(256) void split_weights_stem7_kernel(const float* w
 
 }  // namespace
 
-// ResNet-50's stem on conv_split_stem7_kernel (fp16 form only: the six-product form keeps the float32 kernels there)
-static bool split_stem7(const ConvArgs& a) {
-    static const int on = env_int("POSEPIPE_SPLIT_STEM7", 1);
-    const bool f16 = a.split_f16 != 0 || (a.numerics == 0 && pp_conv_split_f16_default());
-    return on && f16 && a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad_h == 3 && a.pad_w == 3 && a.dil_h == 1 && a.dil_w == 1 &&
-           a.Cin == 4 && a.Cout == 64 && a.CoutPad >= 64 && a.up_log2 == 0 && !a.out_nchw && !a.res1 && !a.res2 &&
-           (a.relu == PP_RELU_NONE || a.relu == PP_RELU_FIRST || a.relu == PP_RELU_LAST) && (a.y_stride == 0 || a.y_stride == a.Cout) &&
-           a.y_coff == 0 && a.Hout == (a.Hin - 1) / 2 + 1 && a.Wout == (a.Win - 1) / 2 + 1;
+// ---- the split plan: whether a layer runs on a split kernel, on which, and with what weight layout (pp_internal.h, SplitPlan) ----------
+
+// the 3x3 tap kernel's tiling of the map for `nw` waves (512-pixel tiles with 8, 256 with 4): the pixel tile that wastes the fewest
+// pixels, or the padded input as one stream where that wastes fewer positions
+static TileGeom tap_tiling(const ConvArgs& a, int nw, int stream_env) {
+    const int max_np = nw == 8 ? 768 : 512, xp_h = a.Hin + a.x_pad, xp_w = a.Win + a.x_pad;
+    TileGeom g = pick_tile(a.Hout, a.Wout, max_np, nw / 2);
+    g.mode = MODE_TILE;
+    const int snp = 64 * nw + 2 + 2 * xp_w;
+    const double stream_eff = (double)a.Hout * a.Wout / ((double)xp_h * xp_w);
+    bool use_stream = a.x_pad >= 1 && snp <= max_np && (g.eff < 0 || stream_eff > g.eff + 0.02);
+    if (stream_env == 0 && g.eff >= 0) use_stream = false;
+    if (stream_env == 1 && a.x_pad >= 1 && snp <= max_np) use_stream = true;
+    if (use_stream) {
+        g.mode = MODE_STREAM;
+        g.PWp = xp_w;
+        g.NP = g.NPp = snp;
+        while (g.NPp % 8 != 4) ++g.NPp;
+    }
+    return g;
 }
 
-// how the split kernel sees the layer: taps (9 / 1) and channels per tap (a full-cover 'valid' conv is a 1x1 over KH*KW*Cin)
-// committed: the layer was selected when its split weights were built (pp_net_create_ex / the caller of pp_conv_split_eligible), so
-// the launch path derives the SAME form from the shape alone -- no knob is read at launch time (ABI 7: nothing is decided at launch)
-// POSEPIPE_SPLIT_S2P=0: the strided-patch form off (A/B runs; read once per process)
-static bool split_s2_patch_on() {
-    static const int on = env_int("POSEPIPE_SPLIT_S2P", 1);
-    return on != 0;
-}
-
-static bool split_shape(const ConvArgs& a, int* taps, int* cin, int* mode, bool committed = false) {
+SplitPlan pp_conv_split_plan(const ConvArgs& a) {
+    // selection knobs, read once per process -- except POSEPIPE_SPLIT_S2_MIN_CIN, read per plan: tests set it to run the tap-gather
+    // form on every shape it supports, whatever the selection rule would pick
+    static const int stem7_on = env_int("POSEPIPE_SPLIT_STEM7", 1);
+    static const int s2_on = env_int("POSEPIPE_SPLIT_S2", 1), s2p_on = env_int("POSEPIPE_SPLIT_S2P", 1);
+    static const int gemm8_on = env_int("POSEPIPE_SPLIT_GEMM8", 1), gemm4_min_c = env_int("POSEPIPE_SPLIT_GEMM4_MIN_C", 64);
+    static const int gemm_min_cin = env_int("POSEPIPE_SPLIT_GEMM_MIN_CIN", 1024);
+    static const int c48_on = env_int("POSEPIPE_SPLIT_C48", 1), c48_mult = env_int("POSEPIPE_SPLIT_C48_MULT", 0);
+    static const int stream_env = env_int("POSEPIPE_SPLIT_STREAM", -1);
+    const char* s2_env = getenv("POSEPIPE_SPLIT_S2_MIN_CIN");
+    SplitPlan p;
+    p.f16 = a.split_f16 != 0;
+    const size_t wpl = p.f16 ? 2 : 3;                   // weight planes: (g0, g1) of the fp16 form, three bf16 planes
+    p.ncb = (a.Cout + 31) / 32;                         // odd: one block per workgroup (COB = 1), else two
+    p.nout = p.ncb * 32;
+    // ResNet-50's stem on conv_split_stem7_kernel (fp16 form only: the six-product form keeps the float32 kernels there)
+    if (stem7_on && p.f16 && a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad_h == 3 && a.pad_w == 3 && a.dil_h == 1 && a.dil_w == 1 &&
+        a.Cin == 4 && a.Cout == 64 && a.CoutPad >= 64 && a.up_log2 == 0 && !a.out_nchw && !a.res1 && !a.res2 &&
+        (a.relu == PP_RELU_NONE || a.relu == PP_RELU_FIRST || a.relu == PP_RELU_LAST) && (a.y_stride == 0 || a.y_stride == a.Cout) &&
+        a.y_coff == 0 && a.Hout == (a.Hin - 1) / 2 + 1 && a.Wout == (a.Win - 1) / 2 + 1) {
+        p.kernel = SPLIT_STEM7;
+        p.cin = a.Cin;
+        p.frag_bytes = STEM_WBYTES;
+        p.bytes = p.frag_bytes + (size_t)2 * p.nout * sizeof(float);
+        return p;
+    }
+    // how the split kernel sees the layer: taps (9 / 1) and channels per tap (a full-cover 'valid' conv is a 1x1 over KH*KW*Cin)
     const bool k3 = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_h == 1 && a.pad_w == 1 && a.dil_h == 1 && a.dil_w == 1 &&
                     a.Hout == a.Hin && a.Wout == a.Win;
     const bool k1 = a.KH == 1 && a.KW == 1 && a.pad_h == 0 && a.pad_w == 0;
@@ -2290,145 +2314,104 @@ static bool split_shape(const ConvArgs& a, int* taps, int* cin, int* mode, bool 
     // 128 / 256 / 512-channel strided 3x3 122 -> 132, 132 -> 139, 135 -> 140 TFLOP/s, HRNet 192 -> 384 98 -> 104; with 48 / 96 input
     // channels or ONE channel block per workgroup (Cout 96) it LOSES to the fp32 kernels (48 -> 96: 95 -> 58), so: from 128 input
     // channels, two channel blocks.  (What these layers want is the patch form with a strided patch: 4x the LDS per tile.)
-    static const int s2_on = env_int("POSEPIPE_SPLIT_S2", 1);
-    // POSEPIPE_SPLIT_S2_MIN_CIN (read per SELECTION, i.e. at net creation: tests set it to run the form on every shape it supports,
-    // whatever the selection rule would pick); a committed layer keeps the form it was created with
-    const char* s2_env = committed ? nullptr : getenv("POSEPIPE_SPLIT_S2_MIN_CIN");
     // Round 5 (fp16 form: half the products of the form the rule above was measured on; same-box per-op tables, W48, 128 samples): 96 -> 192
     // 1.26 -> 1.09 ms, 96 -> 96 0.19 -> 0.16, 96 -> 384 0.18 -> 0.15, 256 -> 96 (three blocks) 0.85 -> 0.67, 48 -> 192 0.55 -> 0.44, 48 -> 384
     // 0.10 -> 0.08; it still LOSES on 48 -> 96 (1.34 -> 2.10) and 48 -> 48 (0.80 -> 0.89): from 96 input channels, or from 48 with >= 6 blocks.
-    const int s2_ncb = (a.Cout + 31) / 32;
-    const bool s2_f16 = a.split_f16 != 0 || (a.numerics == 0 && pp_conv_split_f16_default());
-    const bool s2_pick = committed || (s2_env ? a.Cin >= atoi(s2_env)
-                                              : s2_f16 ? (a.Cin >= 96 || (a.Cin >= 48 && s2_ncb >= 6)) : (a.Cin >= 128 && (s2_ncb & 1) == 0));
+    const bool s2_pick = s2_env ? a.Cin >= atoi(s2_env) : p.f16 ? (a.Cin >= 96 || (a.Cin >= 48 && p.ncb >= 6)) : (a.Cin >= 128 && (p.ncb & 1) == 0);
     // Round 6 (fp16 form): the STRIDED-PATCH form (conv_split_kernel<.., S2>) takes every 3x3 / stride-2 / pad-1 layer -- it stages each input
     // element once and has no padding products, so the break-even rules above do not apply to it.  Same weight fragments ([chunk][tap]
-    // order) as the tap-gather product, which stays the bf16 form's (and POSEPIPE_SPLIT_S2P=0's) kernel: mode MODE_TILE + stride 2.
+    // order) as the tap-gather product, which stays the bf16 form's (and POSEPIPE_SPLIT_S2P=0's) kernel.
     const bool s2_shape = a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad_h == 1 && a.pad_w == 1 && a.dil_h == 1 && a.dil_w == 1 && !full;
     // Same-box per-op tables (profile_net w48 128 / det 64, S2P on / off): 48 -> 96 at 96x72 1.37 -> 0.91 ms (float32 kernel before), 256 -> 96
     // 0.66 -> 0.39, 64 -> 64 at 192x144 0.55 -> 0.37, 96 -> 192 1.07 -> 0.97, 48 -> 48 0.81 -> 0.76; ResNet-50 128 -> 128 at 160x272 1.07 -> 0.88,
     // 256 -> 256 1.01 -> 0.72, 512 -> 512 1.00 -> 0.93.  It LOSES where a 128-pixel tile does not fit the output map: 12x9 outputs (192 -> 384
     // 0.39 -> 0.43, 96 -> 384 0.15 -> 0.16, 48 -> 384 0.09 -> 0.11) and 48 -> 48 onto 24x18 (0.07 -> 0.08) -- those keep their former kernels.
-    // The rule reads the layer's shape only (never the batch, never a knob at launch).
     const bool s2p_map = a.Hout * a.Wout >= 1500 || (a.Hout * a.Wout >= 400 && a.Cout >= 96);
-    const bool s2p = split_s2_patch_on() && s2_f16 && s2_shape && s2p_map;
+    const bool s2p = s2p_on && p.f16 && s2_shape && s2p_map;
     const bool k3s2 = s2_on && s2_shape && (s2_pick || s2p);
-    if (!(k3 || k1 || full || k3s2)) return false;
-    *taps = (k3 || k3s2) ? 9 : 1;
-    *cin = full ? a.K : a.Cin;
-    *mode = (k3 || (k3s2 && s2p)) ? MODE_TILE : MODE_GEMM;
-    return true;
-}
-
-// product kernel (conv_split_gemm_kernel) for 1x1 / full-cover layers: 3 = 256 x 128 tile, 4 waves, two workgroups per CU; 0 = no.
-// Round 4: ONE form.  The per-workgroup timeline (tools/split_timeline.py) showed these layers bound by the CU's memory path, with the
-// epilogue as long as the K loop (256 -> 1024 at 40x68: 64k cycles of loop, 57k of epilogue) -- the 8-wave forms (256 x 256, 512 x 128: one
-// workgroup per CU) had nothing to run beside it.  With the residual lines of the epilogue requested back to back, the two-per-CU
-// form wins on EVERY layer of the detector (per 64 frames, 8-wave form -> this one): 512 -> 2048 1.76 -> 1.48 ms, 512 -> 128 1.74 -> 1.52,
-// 512 -> 256 2.00 -> 1.88, 1024 -> 256 2.88 -> 2.76, 2048 -> 512 1.13 -> 0.90, fc6 (K = 12544) 6.41 -> 6.24 (264 TFLOP/s), and
-// 128 -> 512 leaves the fp32 kernels for it (4.06 -> 3.74); 64 -> 256 stayed there in round 4 (5.59 vs 5.91: profiles/r04_product_kernel_forms.txt).
-// Round 5, after the rewrite of this kernel (pixels by DMA, three stages): 64 -> 256 at 160x272 5.60 -> 4.74 ms per 64 frames (4.08 -> 4.81 TB/s
-// algorithmic), HRNet's 64 -> 256 at 96x72 2.34 -> 2.01 ms per 128 samples, same box -- the floor is 64 input channels now.
-static int gemm8_cfg(const ConvArgs& a, int mode, int cin) {
-    static const int on = env_int("POSEPIPE_SPLIT_GEMM8", 1), min_c4 = env_int("POSEPIPE_SPLIT_GEMM4_MIN_C", 64);
-    const bool tap_gather = a.KH * a.KW > 1 && cin == a.Cin;        // 3x3 stride 2: the tap kernel's product form, not this one
-    if (!on || mode != MODE_GEMM || tap_gather) return 0;
-    return (cin >= min_c4 && a.Cout % 128 == 0) ? 3 : 0;
-}
-
-bool pp_conv_split_eligible(const ConvArgs& a) {
+    if (!(k3 || k1 || full || k3s2)) return p;
+    p.taps = (k3 || k3s2) ? 9 : 1;
+    p.cin = full ? a.K : a.Cin;
+    // product kernel (conv_split_gemm_kernel) for 1x1 / full-cover layers: 256 x 128 tile, 4 waves, two workgroups per CU.
+    // Round 4: ONE form.  The per-workgroup timeline (tools/split_timeline.py) showed these layers bound by the CU's memory path, with the
+    // epilogue as long as the K loop (256 -> 1024 at 40x68: 64k cycles of loop, 57k of epilogue) -- the 8-wave forms (256 x 256, 512 x 128: one
+    // workgroup per CU) had nothing to run beside it.  With the residual lines of the epilogue requested back to back, the two-per-CU
+    // form wins on EVERY layer of the detector (per 64 frames, 8-wave form -> this one): 512 -> 2048 1.76 -> 1.48 ms, 512 -> 128 1.74 -> 1.52,
+    // 512 -> 256 2.00 -> 1.88, 1024 -> 256 2.88 -> 2.76, 2048 -> 512 1.13 -> 0.90, fc6 (K = 12544) 6.41 -> 6.24 (264 TFLOP/s), and
+    // 128 -> 512 leaves the fp32 kernels for it (4.06 -> 3.74); 64 -> 256 stayed there in round 4 (5.59 vs 5.91: profiles/r04_product_kernel_forms.txt).
+    // Round 5, after the rewrite of this kernel (pixels by DMA, three stages): 64 -> 256 at 160x272 5.60 -> 4.74 ms per 64 frames (4.08 -> 4.81 TB/s
+    // algorithmic), HRNet's 64 -> 256 at 96x72 2.34 -> 2.01 ms per 128 samples, same box -- the floor is 64 input channels now.
+    const bool product = gemm8_on && p.taps == 1 && p.cin >= gemm4_min_c && a.Cout % 128 == 0;
+    // 1x1 layers with Cout % 128 == 0: the product kernel.  Others: the tap kernel's one-tap form wins from ~1024 input
+    // channels only (its 256 x 64 tile re-reads X Cout / 64 times; below, the fp32 kernel's smaller tiles do as well or better).
+    // Round 5 (fp16 form): ONE 64-channel column reads X once, and then the one-tap form beats the float32 kernel from 256 input
+    // channels on large maps -- 256 -> 64 at 160x272 1.88 -> 1.62 ms per 64 frames, at 96x72 0.92 -> 0.83 per 128 samples; 12x9 maps
+    // (384 -> 48: 0.05 -> 0.11) and the 16-channel RPN maps lose and stay where they were.
+    const bool one_column = p.f16 && p.cin >= 256 && a.Cout > 32 && a.Cout <= 64 && a.HWout >= 4096;   // (per SAMPLE: the choice must not depend on the batch)
+    if (p.taps == 1 && p.cin < gemm_min_cin && !one_column && !product) return p;
     // res1: the output's own shape, or a coarser map read with >> shift (FPN's lat[i-1] += up(lat[i]), fused as a shifted read)
     const bool res1_plain = !a.res1 || (a.res1_off_w == 0 && a.res1_shift >= 0 && a.res1_shift <= 4 &&
                                         ((a.Hout - 1) >> a.res1_shift) < a.res1_H && ((a.Wout - 1) >> a.res1_shift) < a.res1_W &&
                                         (a.res1_shift > 0 || (a.res1_H == a.Hout && a.res1_W == a.Wout)));
-    int taps, cin, mode;
-    if (split_stem7(a)) return true;
-    // 1x1 layers with Cout % 128 == 0: the 8-wave product kernel.  Others: the tap kernel's one-tap form wins from ~1024 input
-    // channels only (its 256 x 64 tile re-reads X Cout / 64 times; below, the fp32 kernel's smaller tiles do as well or better).
-    static const int gemm_min_cin = env_int("POSEPIPE_SPLIT_GEMM_MIN_CIN", 1024);
-    if (!split_shape(a, &taps, &cin, &mode)) return false;
-    // Round 5 (fp16 form): ONE 64-channel column reads X once, and then the one-tap form beats the float32 kernel from 256 input
-    // channels on large maps -- 256 -> 64 at 160x272 1.88 -> 1.62 ms per 64 frames, at 96x72 0.92 -> 0.83 per 128 samples; 12x9 maps
-    // (384 -> 48: 0.05 -> 0.11) and the 16-channel RPN maps lose and stay where they were.
-    const bool f16_form = a.split_f16 != 0 || (a.numerics == 0 && pp_conv_split_f16_default());
-    const bool one_column = f16_form && cin >= 256 && a.Cout > 32 && a.Cout <= 64 && a.HWout >= 4096;   // (per SAMPLE: the choice must not depend on the batch)
-    if (mode == MODE_GEMM && taps == 1 && cin < gemm_min_cin && !one_column && !gemm8_cfg(a, mode, cin)) return false;
-    return cin % 16 == 0 && a.Cout % 4 == 0 && a.up_log2 == 0 && !a.out_nchw && res1_plain && a.relu <= PP_ACT_SWISH &&
-           (a.y_stride == 0 || a.y_stride == a.Cout) && a.y_coff == 0;
+    if (!(p.cin % 16 == 0 && a.Cout % 4 == 0 && a.up_log2 == 0 && !a.out_nchw && res1_plain && a.relu <= PP_ACT_SWISH &&
+          (a.y_stride == 0 || a.y_stride == a.Cout) && a.y_coff == 0))
+        return p;
+    // 3x3 stride 1 with 33 .. 48 output channels: conv_split48_kernel (three 16-channel blocks, K = two taps x 16 channels)
+    const bool c48 = c48_on && k3 && ((a.Cout > 32 && a.Cout <= 48) || (c48_mult == 1 && a.Cout % 48 == 0) || (c48_mult == 2 && a.Cout == 192));
+    size_t steps = (size_t)(p.cin / 16) * p.taps;
+    if (product) {
+        p.kernel = SPLIT_PRODUCT;
+    } else if (!k3 && !s2p) {
+        p.kernel = p.taps > 1 ? SPLIT_TAP_GATHER : SPLIT_ONE_TAP;
+        p.tile[0].mode = MODE_GEMM;
+        p.tile[0].NP = 256;
+        p.tile[0].NPp = 260;
+    } else if (s2p) {
+        p.kernel = SPLIT_S2P;
+        p.tile[0] = pick_tile_s2(a.Hout, a.Wout, 13 * 64);
+        p.tile[0].mode = MODE_TILE;
+    } else if (c48) {
+        p.kernel = SPLIT_C48;
+        p.ncb = (a.Cout + 47) / 48 * 3;                 // 16-channel blocks, whole columns of 3
+        p.nout = p.ncb * 16;
+        steps = (size_t)(p.cin / 16) * 5;
+        p.tile[0] = tap_tiling(a, 4, stream_env);
+    } else {
+        p.kernel = SPLIT_TAP3;
+        p.tile[0] = tap_tiling(a, 4, stream_env);
+        p.tile[1] = tap_tiling(a, 8, stream_env);
+    }
+    p.frag_bytes = (steps + 1) * p.ncb * wpl * 64 * sizeof(uint4);      // + one spare step: the kernel fetches one step ahead
+    p.bytes = p.frag_bytes + (p.f16 ? (size_t)2 * p.nout * sizeof(float) : 0);   // fp16 form: 1 / c, then max |w| per output channel
+    return p;
 }
 
-static int split_ncb(const ConvArgs& a) { return (a.Cout + 31) / 32; }     // odd: one block per workgroup (COB = 1), else two
-
-// 3x3 stride 1 with 33 .. 48 output channels: conv_split48_kernel (three 16-channel blocks, K = two taps x 16 channels)
-static bool split_c48(const ConvArgs& a) {
-    static const int on = env_int("POSEPIPE_SPLIT_C48", 1), mult = env_int("POSEPIPE_SPLIT_C48_MULT", 0);
-    int taps, cin, mode;
-    const bool shape = (a.Cout > 32 && a.Cout <= 48) || (mult == 1 && a.Cout % 48 == 0) || (mult == 2 && a.Cout == 192);
-    return on && shape && a.stride == 1 && split_shape(a, &taps, &cin, &mode) && mode == MODE_TILE;
-}
-static int split_ncb16(const ConvArgs& a) { return (a.Cout + 47) / 48 * 3; }      // 16-channel blocks, whole columns of 3
-
-// bytes of the fragments ...
-static size_t split_frag_bytes(const ConvArgs& a, bool committed = false) {
-    int taps = 1, cin = a.Cin, mode = 0;
-    split_shape(a, &taps, &cin, &mode, committed);      // (committed: at launch the form is the one the split copy was built for)
-    const size_t wpl = a.split_f16 ? 2 : 3;              // weight planes: (g0, g1) of the fp16 form, three bf16 planes
-    if (split_stem7(a)) return STEM_WBYTES;
-    if (split_c48(a)) return ((size_t)(cin / 16) * 5 + 1) * split_ncb16(a) * wpl * 64 * sizeof(uint4);
-    return ((size_t)(cin / 16) * taps + 1) * split_ncb(a) * wpl * 64 * sizeof(uint4);      // + one spare step: the kernel fetches one step ahead
-}
-// ... and, fp16 form, of what follows them: 1 / c per output channel, then max |w| per output channel
-static int split_nout(const ConvArgs& a) { return split_c48(a) ? split_ncb16(a) * 16 : split_ncb(a) * 32; }
-size_t pp_conv_split_bytes(const ConvArgs& a) {
-    return split_frag_bytes(a) + (a.split_f16 ? (size_t)2 * split_nout(a) * sizeof(float) : 0);
-}
-
-int pp_conv_split_weights(const ConvArgs& a, void* out, hipStream_t stream) {
-    int taps = 1, cin = a.Cin, mode = 0;
-    split_shape(a, &taps, &cin, &mode);
-    const int ncb = split_ncb(a);
-    float* inv_scale = nullptr;
+int pp_conv_split_weights(const SplitPlan& p, const ConvArgs& a, void* out, hipStream_t stream) {
     float* cmax = nullptr;
-    if (a.split_f16) {
-        const int nout = split_nout(a);
-        inv_scale = reinterpret_cast<float*>(static_cast<unsigned char*>(out) + split_frag_bytes(a));
-        cmax = inv_scale + nout;
-        hipLaunchKernelGGL(weight_channel_max_kernel, dim3((unsigned)nout), dim3(64), 0, stream, a.w, a.Kpad / 32, a.CoutPad, nout, cmax, inv_scale);
+    if (p.f16) {
+        float* inv_scale = reinterpret_cast<float*>(static_cast<unsigned char*>(out) + p.frag_bytes);
+        cmax = inv_scale + p.nout;
+        hipLaunchKernelGGL(weight_channel_max_kernel, dim3((unsigned)p.nout), dim3(64), 0, stream, a.w, a.Kpad / 32, a.CoutPad, p.nout, cmax, inv_scale);
     }
-    if (split_stem7(a)) {
+    const char* what = "split_weights";
+    if (p.kernel == SPLIT_STEM7) {
+        what = "split_weights_stem7";
         hipLaunchKernelGGL(split_weights_stem7_kernel, dim3((STEM_STEPS * 2 * 64 + 255) / 256), dim3(256), 0, stream, a.w, (uint4*)out, a.CoutPad, cmax);
-        hipError_t es = hipGetLastError();
-        if (es != hipSuccess) {
-            pp_set_error("split_weights_stem7 launch failed: %s", hipGetErrorString(es));
-            return PP_ERR_HIP;
-        }
-        return PP_OK;
+    } else if (p.kernel == SPLIT_C48) {
+        what = "split_weights48";
+        const size_t total = (size_t)(p.cin / 16) * 5 * p.ncb * 64;
+        const dim3 grid((unsigned)((total + 255) / 256));
+        if (p.f16) hipLaunchKernelGGL(split_weights48_kernel<true>, grid, dim3(256), 0, stream, a.w, (uint4*)out, p.cin, a.CoutPad, p.ncb, total, cmax);
+        else hipLaunchKernelGGL(split_weights48_kernel<false>, grid, dim3(256), 0, stream, a.w, (uint4*)out, p.cin, a.CoutPad, p.ncb, total, cmax);
+    } else {
+        const size_t total = (size_t)(p.cin / 16) * p.taps * p.ncb * 64;
+        const dim3 grid((unsigned)((total + 255) / 256));
+        if (p.f16) hipLaunchKernelGGL(split_weights_kernel<true>, grid, dim3(256), 0, stream, a.w, (uint4*)out, p.cin, p.taps, a.CoutPad, p.ncb, total, cmax);
+        else hipLaunchKernelGGL(split_weights_kernel<false>, grid, dim3(256), 0, stream, a.w, (uint4*)out, p.cin, p.taps, a.CoutPad, p.ncb, total, cmax);
     }
-    if (split_c48(a)) {
-        const size_t total48 = (size_t)(cin / 16) * 5 * split_ncb16(a) * 64;
-        if (a.split_f16)
-            hipLaunchKernelGGL(split_weights48_kernel<true>, dim3((unsigned)((total48 + 255) / 256)), dim3(256), 0, stream, a.w, (uint4*)out, cin,
-                               a.CoutPad, split_ncb16(a), total48, cmax);
-        else
-        hipLaunchKernelGGL(split_weights48_kernel<false>, dim3((unsigned)((total48 + 255) / 256)), dim3(256), 0, stream, a.w, (uint4*)out, cin,
-                           a.CoutPad, split_ncb16(a), total48, cmax);
-        hipError_t e48 = hipGetLastError();
-        if (e48 != hipSuccess) {
-            pp_set_error("split_weights48 launch failed: %s", hipGetErrorString(e48));
-            return PP_ERR_HIP;
-        }
-        return PP_OK;
-    }
-    const size_t total = (size_t)(cin / 16) * taps * ncb * 64;
-    if (a.split_f16)
-        hipLaunchKernelGGL(split_weights_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.w, (uint4*)out, cin,
-                           taps, a.CoutPad, ncb, total, cmax);
-    else
-    hipLaunchKernelGGL(split_weights_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.w, (uint4*)out, cin,
-                       taps, a.CoutPad, ncb, total, cmax);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        pp_set_error("split_weights launch failed: %s", hipGetErrorString(e));
+        pp_set_error("%s launch failed: %s", what, hipGetErrorString(e));
         return PP_ERR_HIP;
     }
     return PP_OK;
@@ -2518,6 +2501,55 @@ static void fill_divisors(SplitArgs& s) {
     make_magic((unsigned)std::max(s.KW, 1), s.dv_kw);
 }
 
+// launches kernel K with `lds` bytes of dynamic LDS; more than 64 KB has to be allowed per kernel, once per device (up to MAX_LDS)
+template <auto K, int MAX_LDS, class Args>
+static void launch_split(dim3 grid, unsigned threads, size_t lds, hipStream_t stream, const Args& s) {
+    static PpPerDeviceOnce once;
+    once.run([] { (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS); });
+    hipLaunchKernelGGL(K, grid, dim3(threads), lds, stream, s);
+}
+
+// calls f(std::integral_constant<int, NS>) for the first NS of the list with room for nslot patch slots per thread (else the last)
+template <int NS, int... MORE, class F>
+static void with_nslot(int nslot, F&& f) {
+    if constexpr (sizeof...(MORE) == 0) f(std::integral_constant<int, NS>());
+    else if (nslot <= NS) f(std::integral_constant<int, NS>());
+    else with_nslot<MORE...>(nslot, f);
+}
+
+// the tap kernel conv_split_kernel<T, NS, COB, 2, NW, RING4, H> for this launch's channel blocks per wave and split form (three / four
+// blocks: the fp16 form's 4-wave ring kernels only)
+template <int T, int NW, bool R4, int NS>
+static void launch_tap(int cob, bool f16, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s) {
+    constexpr int L = (NW == 8 ? 160 : 100) * 1024;
+    if constexpr (R4) {
+        if (cob == 3) return launch_split<conv_split_kernel<9, NS, 3, 2, 4, true, true>, L>(grid, 256, lds, stream, s);
+        if (cob == 4) return launch_split<conv_split_kernel<9, NS, 4, 2, 4, true, true>, L>(grid, 256, lds, stream, s);
+    }
+    if (f16 && cob == 2) launch_split<conv_split_kernel<T, NS, 2, 2, NW, R4, true>, L>(grid, 64 * NW, lds, stream, s);
+    else if (f16) launch_split<conv_split_kernel<T, NS, 1, 2, NW, R4, true>, L>(grid, 64 * NW, lds, stream, s);
+    else if (cob == 2) launch_split<conv_split_kernel<T, NS, 2, 2, NW, R4, false>, L>(grid, 64 * NW, lds, stream, s);
+    else launch_split<conv_split_kernel<T, NS, 1, 2, NW, R4, false>, L>(grid, 64 * NW, lds, stream, s);
+}
+
+// the plan's pixel tiling (TileGeom) in the launch arguments, and the workgroups it takes for this batch
+static unsigned apply_tiling(SplitArgs& s, const TileGeom& g, const ConvArgs& a, int nw) {
+    s.mode = g.mode;
+    s.NP = g.NP;
+    s.NPp = g.NPp;
+    if (g.mode == MODE_GEMM) {
+        s.S = (long long)a.M;
+        return (unsigned)((a.M + 255) / 256);
+    }
+    s.PWp = g.PWp;
+    if (g.mode == MODE_STREAM) {
+        s.S = (long long)a.N * s.xp_h * s.xp_w;
+        return (unsigned)((s.S + 64 * nw - 1) / (64 * nw));
+    }
+    s.tiles_x = g.tiles_x; s.tiles_y = g.tiles_y; s.TH = g.TH; s.TW = g.TW; s.bw_log2 = g.bw_log2; s.gx_log2 = g.gx_log2;
+    return (unsigned)(g.tiles_x * g.tiles_y * a.N);
+}
+
 static int launch_stem7(const ConvArgs& a, hipStream_t stream) {
     if (!a.x_amax) {
         pp_set_error("conv_split: the fp16 form needs the per-sample maximum of its input (ConvArgs::x_amax)");
@@ -2540,10 +2572,7 @@ static int launch_stem7(const ConvArgs& a, hipStream_t stream) {
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
     }();
-    static PpPerDeviceOnce once;
-    once.run([] { (void)hipFuncSetAttribute((const void*)conv_split_stem7_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEM_LDS); });
-    const unsigned grid = (unsigned)std::min(s.ntiles, ncu);
-    hipLaunchKernelGGL(conv_split_stem7_kernel, dim3(grid), dim3(512), STEM_LDS, stream, s);
+    launch_split<conv_split_stem7_kernel, STEM_LDS>(dim3((unsigned)std::min(s.ntiles, ncu)), 512, STEM_LDS, stream, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         pp_set_error("conv_split_stem7 launch failed: %s", hipGetErrorString(e));
@@ -2552,18 +2581,24 @@ static int launch_stem7(const ConvArgs& a, hipStream_t stream) {
     return PP_OK;
 }
 
-int pp_launch_conv_split(const ConvArgs& a, hipStream_t stream) {
-    int taps = 1, cin = a.Cin, mode = 0;
-    if (a.wsplit && split_stem7(a)) return launch_stem7(a, stream);
-    if (!a.wsplit || !split_shape(a, &taps, &cin, &mode, true)) {
+int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stream) {
+    if (a.wsplit && p.kernel == SPLIT_STEM7) return launch_stem7(a, stream);
+    if (!a.wsplit || p.kernel == SPLIT_NONE) {
         pp_set_error("conv_split: layer not eligible");
         return PP_ERR_ARG;
     }
-    const bool full = mode == MODE_GEMM && cin != a.Cin;
+    // launch-time knobs, read once per process (the product kernel's epilogue also follows pp_debug_knob, per launch)
+    static const int colmaj_mb = env_int("POSEPIPE_SPLIT_COLMAJOR_MB", 256), gemm_remap = env_int("POSEPIPE_SPLIT_GEMM_REMAP", 1);
+    static const int epi_env = env_int("POSEPIPE_SPLIT_GEMM_EPI", 1);
+    static const int cob2_env = env_int("POSEPIPE_SPLIT_S2_COB", 0), cob_env = env_int("POSEPIPE_SPLIT_COB", 0);
+    static const int nw8_f16 = env_int("POSEPIPE_SPLIT_NW8_F16", 0);
+    static const int nw8_min_blocks = env_int("POSEPIPE_SPLIT_NW8_MIN_BLOCKS", 512), nw8_min_chunks = env_int("POSEPIPE_SPLIT_NW8_MIN_CHUNKS", 16);
+    static const int ring4_env = env_int("POSEPIPE_SPLIT_RING4", 1), ring48_env = env_int("POSEPIPE_SPLIT_RING48", 1);
+    const bool full = p.cin != a.Cin;
     SplitArgs s{};
     s.x = a.x; s.w = (const uint4*)a.wsplit; s.bias = a.bias; s.res1 = a.res1; s.res2 = a.res2; s.y = a.y;
-    s.N = a.N; s.H = a.Hout; s.W = a.Wout; s.Cin = cin; s.Cout = a.Cout;
-    s.ncb = split_ncb(a);
+    s.N = a.N; s.H = a.Hout; s.W = a.Wout; s.Cin = p.cin; s.Cout = a.Cout;
+    s.ncb = p.ncb;
     s.xp_h = full ? 1 : a.Hin + a.x_pad;
     s.xp_w = full ? 1 : a.Win + a.x_pad;
     s.stride = a.stride;
@@ -2571,18 +2606,18 @@ int pp_launch_conv_split(const ConvArgs& a, hipStream_t stream) {
     s.r1_shift = a.res1 ? a.res1_shift : 0;
     s.r1_H = a.res1 ? a.res1_H : a.Hout;
     s.r1_W = a.res1 ? a.res1_W : a.Wout;
-    s.nchunks = cin / 16;
+    s.nchunks = p.cin / 16;
     s.ktaps = 1; s.KW = a.KW; s.pad = a.pad_h; s.Hin = a.Hin; s.Win = a.Win;
-    if (mode == MODE_GEMM && taps > 1) {     // tap-gather product: a step per (chunk, tap), weights in the same [chunk][tap] order
-        s.ktaps = taps;
-        s.nchunks = (cin / 16) * taps;
+    if (p.kernel == SPLIT_TAP_GATHER) {     // a step per (chunk, tap), weights in the same [chunk][tap] order
+        s.ktaps = p.taps;
+        s.nchunks = (p.cin / 16) * p.taps;
     }
     s.x_bytes = a.x_bytes;
     s.xcd_remap = a.xcd_remap;
-    const bool f16 = a.split_f16 != 0;
+    const bool f16 = p.f16 != 0;
     const int xp = f16 ? 2 : 3;              // activation planes in LDS
     const int wpl = f16 ? 2 : 3;             // weight planes per fragment set
-    s.wscale = f16 ? reinterpret_cast<const float*>(static_cast<const unsigned char*>(a.wsplit) + split_frag_bytes(a, true)) : nullptr;
+    s.wscale = f16 ? reinterpret_cast<const float*>(static_cast<const unsigned char*>(a.wsplit) + p.frag_bytes) : nullptr;
     s.x_amax = a.x_amax;
     s.y_amax = a.y_amax;
     if (f16 && !a.x_amax) {
@@ -2591,23 +2626,21 @@ int pp_launch_conv_split(const ConvArgs& a, hipStream_t stream) {
     }
     PP_TL_BEGIN();
     // inputs beyond the Infinity Cache (256 MB): the columns of a tile back to back; smaller ones: column by column
-    static const int colmaj_mb = env_int("POSEPIPE_SPLIT_COLMAJOR_MB", 256);
     s.col_major = (size_t)a.x_bytes <= (size_t)colmaj_mb << 20;
-    if (const int g8 = gemm8_cfg(a, mode, cin)) {
+    const char* tag;
+    dim3 grid;
+    if (p.kernel == SPLIT_PRODUCT) {
         s.mode = MODE_GEMM;
         s.S = (long long)a.M;
         s.col_major = 0;                     // the product kernel walks tile by tile, all columns of a tile back to back
         const int BM = 256, BN = 128;
-        dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.Cout / BN));
+        grid = dim3((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.Cout / BN));
         s.gx = (int)grid.x; s.gy = (int)grid.y;
-        static const int gemm_remap = env_int("POSEPIPE_SPLIT_GEMM_REMAP", 1);
         s.xcd_remap = gemm_remap && s.gy > 1;
         if (s.xcd_remap) grid = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
-        else s.xcd_remap = 0;
         // 1 = epilogue transposed through LDS (18 KiB per wave), 0 = from registers: two store orders of the SAME values (bit-identical,
         // tests/test_gpu_split.py A/Bs them in one process through pp_debug_knob("split_gemm_epilogue", ..)); POSEPIPE_SPLIT_GEMM_EPI is
         // read ONCE per process -- no environment scan per launch
-        static const int epi_env = [] { const char* e = getenv("POSEPIPE_SPLIT_GEMM_EPI"); return e ? atoi(e) : 1; }();
         const int epi_knob = g_split_gemm_epi.load(std::memory_order_relaxed);
         s.epi_lds = epi_knob >= 0 ? epi_knob : epi_env;
         const int nwave = 4;
@@ -2615,243 +2648,105 @@ int pp_launch_conv_split(const ConvArgs& a, hipStream_t stream) {
         // fp16 form: three raw float32 pixel stages of BM x 64 B + three weight stages; six-product form: two stages of split planes + weights
         const size_t lds_loop = f16 ? (size_t)3 * BM * 64 + (size_t)3 * BN * 2 * wpl * 16 : (size_t)2 * (xp * 2 * (BM + 4) * 16 + BN * 2 * wpl * 16);
         const size_t lds = std::max<size_t>(lds_loop, s.epi_lds ? (size_t)nwave * (16384 + 2048) : 0);
-        static PpPerDeviceOnce once;
-        once.run([] {
-            (void)hipFuncSetAttribute((const void*)conv_split_gemm_kernel<2, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_split_gemm_kernel<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        });
-        if (f16) hipLaunchKernelGGL((conv_split_gemm_kernel<2, 2, true>), grid, dim3(256), lds, stream, s);
-        else hipLaunchKernelGGL((conv_split_gemm_kernel<2, 2, false>), grid, dim3(256), lds, stream, s);
-        PP_TL_END("g256x128", grid.x * grid.y);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            pp_set_error("conv_split_gemm launch failed: %s", hipGetErrorString(e));
-            return PP_ERR_HIP;
-        }
-        return PP_OK;
-    }
-    // channel blocks (32 output channels) per wave = per workgroup column.  fp16 form, 4-wave ring kernels: THREE where the block
-    // count allows and enough workgroups remain (96 / 192 channels of HRNet-W48): 10 fragment reads per 18 MFMAs and wave instead
-    // of 6 per 6 (96 channels ran with ONE block per workgroup: three columns, each staging the patch again) or 8 per 12.
-    // Same-box A/B (profile_net w48 128): 96 -> 96 at 48x36 292 -> 315 TFLOP/s, 192 -> 192 at 24x18 328 -> 349; 384 -> 384 at 12x9
-    // LOSES (296 -> 227: 308 workgroups on 512 slots) -- hence the workgroup floor below.  FOUR blocks (128, 256, 512 channels: the
-    // detector's 3x3 layers; 12 reads per 24 MFMAs, half the patch staging per output): 128 accumulator registers leave room for ONE
-    // weight register set (WSETS; with two the K loop spilled: 442 -> 215 TFLOP/s) -- 256 -> 256 at 160x272 429 -> 455 TFLOP/s,
-    // 80x136 409 -> 426, 40x68 386 -> 394.
-    if (mode == MODE_TILE && a.stride == 2) {
+        if (f16) launch_split<conv_split_gemm_kernel<2, 2, true>, 80 * 1024>(grid, 256, lds, stream, s);
+        else launch_split<conv_split_gemm_kernel<2, 2, false>, 80 * 1024>(grid, 256, lds, stream, s);
+        tag = "g256x128";
+    } else if (p.kernel == SPLIT_S2P) {
         // strided-patch form: 128-pixel tiles, one pixel block per wave, 1 .. 4 channel blocks per wave (the widest the block count and
         // the LDS budget allow: every column stages the patch again)
-        static const int cob2_env = env_int("POSEPIPE_SPLIT_S2_COB", 0);
-        const TileGeom g = pick_tile_s2(a.Hout, a.Wout, 13 * 64);
-        if (g.eff < 0) {
+        if (p.tile[0].eff < 0) {
             pp_set_error("conv_split: no strided-patch tile for a %dx%d map", a.Hout, a.Wout);
             return PP_ERR_STATE;
         }
-        s.mode = MODE_TILE;
-        s.tiles_x = g.tiles_x; s.tiles_y = g.tiles_y; s.TH = g.TH; s.TW = g.TW; s.bw_log2 = g.bw_log2; s.gx_log2 = g.gx_log2;
-        s.PWp = g.PWp; s.NP = g.NP; s.NPp = g.NPp;
-        s.SP = (g.TH + 1) * g.PWp;
-        const unsigned gx2 = (unsigned)(g.tiles_x * g.tiles_y * a.N);
-        int cob2 = 1;
+        const unsigned gx = apply_tiling(s, p.tile[0], a, 4);
+        s.SP = (s.TH + 1) * s.PWp;
+        int cob = 1;
         for (int c : {4, 3, 2})
             if (s.ncb % c == 0 && (size_t)2 * 2 * s.NPp * 16 + (size_t)4 * c * 2 * 1024 <= 80 * 1024 && (cob2_env == 0 || cob2_env == c)) {
-                cob2 = c;
+                cob = c;
                 break;
             }
-        const int nslot2 = (s.NP + 63) / 64;
-        dim3 grid2(gx2, (unsigned)(s.ncb / cob2));
-        s.gx = (int)grid2.x; s.gy = (int)grid2.y;
-        if (s.xcd_remap) grid2 = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
+        grid = dim3(gx, (unsigned)(s.ncb / cob));
+        s.gx = (int)grid.x; s.gy = (int)grid.y;
+        if (s.xcd_remap) grid = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
         fill_divisors(s);
         make_magic((unsigned)s.SP, s.dv_row);          // (this form decodes a patch slot into (phase, row, column): dv_row = 1 / SP)
-        const size_t lds2 = (size_t)2 * 2 * s.NPp * 16 + (size_t)4 * cob2 * 2 * 1024;
-#define PP_SPLIT_LAUNCH_S2(NS_, COB_)                                                                                   \
-    do {                                                                                                                \
-        static PpPerDeviceOnce once;                                                                                    \
-        once.run([] {                                                                                                   \
-            (void)hipFuncSetAttribute((const void*)conv_split_kernel<9, NS_, COB_, 1, 4, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-        });                                                                                                             \
-        hipLaunchKernelGGL((conv_split_kernel<9, NS_, COB_, 1, 4, true, true, true>), grid2, dim3(256), lds2, stream, s); \
-    } while (0)
-#define PP_SPLIT_LAUNCH_S2_NS(COB_)                                                                                     \
-    do {                                                                                                                \
-        if (nslot2 <= 10) PP_SPLIT_LAUNCH_S2(10, COB_);                                                                 \
-        else if (nslot2 == 11) PP_SPLIT_LAUNCH_S2(11, COB_);                                                            \
-        else PP_SPLIT_LAUNCH_S2(13, COB_);                                                                              \
-    } while (0)
-        if (cob2 == 4) PP_SPLIT_LAUNCH_S2_NS(4);
-        else if (cob2 == 3) PP_SPLIT_LAUNCH_S2_NS(3);
-        else if (cob2 == 2) PP_SPLIT_LAUNCH_S2_NS(2);
-        else PP_SPLIT_LAUNCH_S2_NS(1);
-        PP_TL_END("s2p", grid2.x * grid2.y);
-        hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) {
-            pp_set_error("conv_split (strided patch) launch failed: %s", hipGetErrorString(e2));
-            return PP_ERR_HIP;
-        }
-        return PP_OK;
-    }
-    static const int cob_env = env_int("POSEPIPE_SPLIT_COB", 0);
-    const bool cob_wide_ok = a.split_f16 != 0 && mode != MODE_GEMM && !split_c48(a);
-    int cob = (s.ncb & 1) ? 1 : 2;
-    if (cob_wide_ok && s.ncb % 3 == 0 && (cob_env == 0 || cob_env == 3)) cob = 3;
-    else if (cob_wide_ok && s.ncb % 4 == 0 && (cob_env == 0 || cob_env == 4)) cob = 4;
-    static const int stream_env = env_int("POSEPIPE_SPLIT_STREAM", -1);
-    static const int nw8_min_blocks = env_int("POSEPIPE_SPLIT_NW8_MIN_BLOCKS", 512), nw8_min_chunks = env_int("POSEPIPE_SPLIT_NW8_MIN_CHUNKS", 16);
-    unsigned gx = 0;
-    const bool c48 = split_c48(a);
-    // fp16 form: the 4-wave ring form everywhere.  With half the matrix work per tap both forms sit at the same ~420 TFLOP/s on the
-    // long-K layers (LDS bandwidth: 8 b128 fragment reads per 12 MFMAs and wave), and two workgroups per CU hide each other's per-tap
-    // barrier: same-box A/B (profile_net det 64) 256 -> 256 at 160x272 414.7 -> 418.9, 80x136 366 -> 400, 40x68 354 -> 371 TFLOP/s
-    static const int nw8_f16 = env_int("POSEPIPE_SPLIT_NW8_F16", 0);
-    int nw = (c48 || (f16 && !nw8_f16)) ? 4 : 8;
-    // geometry for the 8-wave form (512-pixel tiles, one workgroup per CU); if that gives fewer than ~2 workgroups per CU (or
-    // the layer is a one-tap product), the 4-wave form (256-pixel tiles, two per CU)
-    for (;;) {
-        const int tile_px = 64 * nw, pxb = nw / 2;
-        if (mode == MODE_GEMM) {
-            nw = 4;
-            s.mode = MODE_GEMM;
-            s.S = (long long)a.M;
-            s.NP = 256;
-            s.NPp = 260;
-            gx = (unsigned)((a.M + 255) / 256);
-            break;
-        }
-        const int max_np = nw == 8 ? 768 : 512;
-        const TileGeom g = pick_tile(a.Hout, a.Wout, max_np, pxb);
-        const int snp = tile_px + 2 + 2 * s.xp_w;
-        const double stream_eff = (double)a.Hout * a.Wout / ((double)s.xp_h * s.xp_w);
-        bool use_stream = a.x_pad >= 1 && snp <= max_np && (g.eff < 0 || stream_eff > g.eff + 0.02);
-        if (stream_env == 0 && g.eff >= 0) use_stream = false;
-        if (stream_env == 1 && a.x_pad >= 1 && snp <= max_np) use_stream = true;
-        if (use_stream) {
-            s.mode = MODE_STREAM;
-            s.PWp = s.xp_w;
-            s.S = (long long)a.N * s.xp_h * s.xp_w;
-            s.NP = snp;
-            s.NPp = snp;
-            while (s.NPp % 8 != 4) ++s.NPp;
-            gx = (unsigned)((s.S + tile_px - 1) / tile_px);
-        } else {
-            s.mode = MODE_TILE;
-            s.tiles_x = g.tiles_x; s.tiles_y = g.tiles_y; s.TH = g.TH; s.TW = g.TW; s.bw_log2 = g.bw_log2; s.gx_log2 = g.gx_log2;
-            s.PWp = g.PWp; s.NP = g.NP; s.NPp = g.NPp;
-            gx = (unsigned)(g.tiles_x * g.tiles_y * a.N);
-        }
-        // measured on real activations (zeros clock ~15 % higher and mislead): 256 -> 256 at 160x272 207 -> 227 TFLOP/s, at 40x68
-        // 186 -> 199; but 128 -> 128 189 -> 182 and HRNet's 48 / 96-channel layers -8 %: the per-tap barrier and the three-DMA
-        // start-up want >= 16 chunks to pay off
-        if (nw == 4 || ((long)gx * (s.ncb / cob) >= nw8_min_blocks && s.nchunks >= nw8_min_chunks)) break;
-        nw = 4;
-    }
-    const int nslot = (s.NP + 16 * nw - 1) / (16 * nw);     // exactly: only the last patch slot of a thread can be partly outside
-    // (three / four blocks per wave exist for the 4-wave ring kernels only: back to one / two where that form does not apply)
-    static const int ring4_env0 = env_int("POSEPIPE_SPLIT_RING4", 1);
-    if (cob >= 3 && !(ring4_env0 && nw == 4 && (size_t)xp * 2 * s.NPp * 16 + (size_t)4 * cob * wpl * 1024 <= 80 * 1024 &&
-                      (cob_env >= 3 || (long)gx * (s.ncb / cob) >= 400)))
-        cob = (s.ncb & 1) ? 1 : 2;
-    dim3 grid(gx, (unsigned)(s.ncb / cob));
-    s.gx = (int)grid.x; s.gy = (int)grid.y;
-    if (s.xcd_remap) grid = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
-    if (c48) {
+        const size_t lds = (size_t)2 * 2 * s.NPp * 16 + (size_t)4 * cob * 2 * 1024;
+        with_nslot<10, 11, 13>((s.NP + 63) / 64, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value, L = 100 * 1024;
+            if (cob == 4) launch_split<conv_split_kernel<9, NS, 4, 1, 4, true, true, true>, L>(grid, 256, lds, stream, s);
+            else if (cob == 3) launch_split<conv_split_kernel<9, NS, 3, 1, 4, true, true, true>, L>(grid, 256, lds, stream, s);
+            else if (cob == 2) launch_split<conv_split_kernel<9, NS, 2, 1, 4, true, true, true>, L>(grid, 256, lds, stream, s);
+            else launch_split<conv_split_kernel<9, NS, 1, 1, 4, true, true, true>, L>(grid, 256, lds, stream, s);
+        });
+        tag = "s2p";
+    } else if (p.kernel == SPLIT_C48) {
         // three 16-channel blocks per workgroup on v_mfma_f32_16x16x32_bf16; Cout / 48 channel columns
-        s.ncb = split_ncb16(a);
+        const unsigned gx = apply_tiling(s, p.tile[0], a, 4);
+        s.gx = (int)gx;
         s.gy = s.ncb / 3;
-        if (s.xcd_remap) grid = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
-        else grid = dim3(gx, (unsigned)s.gy);
+        grid = s.xcd_remap ? dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1) : dim3(gx, (unsigned)s.gy);
         fill_divisors(s);
         // fp16 form: weights through a 4-slot LDS ring (3 blocks x 2 planes = 6 KB per pair-step) where patch + ring leave two workgroups per CU
-        static const int ring48_env = env_int("POSEPIPE_SPLIT_RING48", 1);
         const size_t patch48 = (size_t)2 * xp * 2 * s.NPp * 16;
         const bool ring48 = f16 && ring48_env && patch48 + (size_t)4 * 3 * wpl * 1024 <= 80 * 1024;
-        const size_t lds48 = patch48 + (ring48 ? (size_t)4 * 3 * wpl * 1024 : 0);
-#define PP_SPLIT48_LAUNCH(NS_)                                                                                          \
-    do {                                                                                                                \
-        static PpPerDeviceOnce once;                                                                                     \
-        once.run([] {                                                                                       \
-            (void)hipFuncSetAttribute((const void*)conv_split48_kernel<NS_, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-            (void)hipFuncSetAttribute((const void*)conv_split48_kernel<NS_, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-            (void)hipFuncSetAttribute((const void*)conv_split48_kernel<NS_, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-        });                                                                                                             \
-        if (ring48) hipLaunchKernelGGL((conv_split48_kernel<NS_, true, true>), grid, dim3(256), lds48, stream, s);      \
-        else if (f16) hipLaunchKernelGGL((conv_split48_kernel<NS_, true, false>), grid, dim3(256), lds48, stream, s);   \
-        else hipLaunchKernelGGL((conv_split48_kernel<NS_, false, false>), grid, dim3(256), lds48, stream, s);           \
-    } while (0)
-        if (nslot <= 5) PP_SPLIT48_LAUNCH(5);
-        else if (nslot == 6) PP_SPLIT48_LAUNCH(6);
-        else if (nslot == 7) PP_SPLIT48_LAUNCH(7);
-        else PP_SPLIT48_LAUNCH(8);
-        PP_TL_END("c48", grid.x * grid.y);
-        hipError_t e48 = hipGetLastError();
-        if (e48 != hipSuccess) {
-            pp_set_error("conv_split48 launch failed: %s", hipGetErrorString(e48));
-            return PP_ERR_HIP;
+        const size_t lds = patch48 + (ring48 ? (size_t)4 * 3 * wpl * 1024 : 0);
+        with_nslot<5, 6, 7, 8>((s.NP + 63) / 64, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value, L = 100 * 1024;
+            if (ring48) launch_split<conv_split48_kernel<NS, true, true>, L>(grid, 256, lds, stream, s);
+            else if (f16) launch_split<conv_split48_kernel<NS, true, false>, L>(grid, 256, lds, stream, s);
+            else launch_split<conv_split48_kernel<NS, false, false>, L>(grid, 256, lds, stream, s);
+        });
+        tag = "c48";
+    } else {
+        // the tap kernel: 3x3 stride 1 (tile or stream), or its product form (one-tap, tap-gather).  Channel blocks (32 output channels)
+        // per wave = per workgroup column.  fp16 form, 4-wave ring kernels: THREE where the block count allows and enough workgroups
+        // remain (96 / 192 channels of HRNet-W48): 10 fragment reads per 18 MFMAs and wave instead of 6 per 6 (96 channels ran with ONE
+        // block per workgroup: three columns, each staging the patch again) or 8 per 12.  Same-box A/B (profile_net w48 128): 96 -> 96 at
+        // 48x36 292 -> 315 TFLOP/s, 192 -> 192 at 24x18 328 -> 349; 384 -> 384 at 12x9 LOSES (296 -> 227: 308 workgroups on 512 slots) --
+        // hence the workgroup floor below.  FOUR blocks (128, 256, 512 channels: the detector's 3x3 layers; 12 reads per 24 MFMAs, half
+        // the patch staging per output): 128 accumulator registers leave room for ONE weight register set (WSETS; with two the K loop
+        // spilled: 442 -> 215 TFLOP/s) -- 256 -> 256 at 160x272 429 -> 455 TFLOP/s, 80x136 409 -> 426, 40x68 386 -> 394.
+        const bool tap3 = p.kernel == SPLIT_TAP3;
+        int cob = (s.ncb & 1) ? 1 : 2;
+        if (tap3 && f16 && s.ncb % 3 == 0 && (cob_env == 0 || cob_env == 3)) cob = 3;
+        else if (tap3 && f16 && s.ncb % 4 == 0 && (cob_env == 0 || cob_env == 4)) cob = 4;
+        // fp16 form: the 4-wave ring form everywhere.  With half the matrix work per tap both forms sit at the same ~420 TFLOP/s on the
+        // long-K layers (LDS bandwidth: 8 b128 fragment reads per 12 MFMAs and wave), and two workgroups per CU hide each other's per-tap
+        // barrier: same-box A/B (profile_net det 64) 256 -> 256 at 160x272 414.7 -> 418.9, 80x136 366 -> 400, 40x68 354 -> 371 TFLOP/s.
+        // The 8-wave form (512-pixel tiles, one workgroup per CU) where it gives ~2 workgroups per CU, else the 4-wave form (256-pixel
+        // tiles, two per CU).  Measured on real activations (zeros clock ~15 % higher and mislead): 256 -> 256 at 160x272 207 -> 227
+        // TFLOP/s, at 40x68 186 -> 199; but 128 -> 128 189 -> 182 and HRNet's 48 / 96-channel layers -8 %: the per-tap barrier and the
+        // three-DMA start-up want >= 16 chunks to pay off
+        int nw = tap3 && (!f16 || nw8_f16) ? 8 : 4;
+        unsigned gx = apply_tiling(s, p.tile[nw == 8], a, nw);
+        if (nw == 8 && !((long)gx * (s.ncb / cob) >= nw8_min_blocks && s.nchunks >= nw8_min_chunks)) {
+            nw = 4;
+            gx = apply_tiling(s, p.tile[0], a, nw);
         }
-        return PP_OK;
+        const int nslot = (s.NP + 16 * nw - 1) / (16 * nw);     // exactly: only the last patch slot of a thread can be partly outside
+        // 4 waves, 3x3: weights through the LDS ring with a single-buffered patch (RING4), two workgroups per CU; three / four blocks per
+        // wave exist for the ring kernels only: back to one / two where that form does not apply
+        const auto ring_fits = [&](int c) {
+            return ring4_env && nw == 4 && s.mode != MODE_GEMM && (size_t)xp * 2 * s.NPp * 16 + (size_t)4 * c * wpl * 1024 <= 80 * 1024;
+        };
+        if (cob >= 3 && !(ring_fits(cob) && (cob_env >= 3 || (long)gx * (s.ncb / cob) >= 400))) cob = (s.ncb & 1) ? 1 : 2;
+        const bool ring = ring_fits(cob);
+        grid = dim3(gx, (unsigned)(s.ncb / cob));
+        s.gx = (int)grid.x; s.gy = (int)grid.y;
+        if (s.xcd_remap) grid = dim3((unsigned)((s.gx + 7) / 8 * 8 * s.gy), 1);
+        const size_t lds = (size_t)(ring ? 1 : 2) * xp * 2 * s.NPp * 16 + ((nw == 8 || ring) ? (size_t)4 * cob * wpl * 1024 : 0);
+        fill_divisors(s);
+        if (s.mode == MODE_GEMM) launch_tap<1, 4, false, 4>(cob, f16, grid, lds, stream, s);
+        else if (nw == 8) with_nslot<5, 6>(nslot, [&](auto ns) { launch_tap<9, 8, false, decltype(ns)::value>(cob, f16, grid, lds, stream, s); });
+        else if (ring) with_nslot<5, 6, 7, 8>(nslot, [&](auto ns) { launch_tap<9, 4, true, decltype(ns)::value>(cob, f16, grid, lds, stream, s); });
+        else with_nslot<5, 6, 7, 8>(nslot, [&](auto ns) { launch_tap<9, 4, false, decltype(ns)::value>(cob, f16, grid, lds, stream, s); });
+        tag = s.mode == MODE_GEMM ? "gemm4" : nw == 8 ? "nw8" : ring ? "ring4" : "nw4";
     }
-    // 4 waves, 3x3: weights through the LDS ring with a single-buffered patch (RING4), two workgroups per CU
-    static const int ring4_env = env_int("POSEPIPE_SPLIT_RING4", 1);
-    const bool ring4 = ring4_env && nw == 4 && mode != MODE_GEMM && (size_t)xp * 2 * s.NPp * 16 + (size_t)4 * cob * wpl * 1024 <= 80 * 1024;
-    const size_t lds = (size_t)(ring4 ? 1 : 2) * xp * 2 * s.NPp * 16 + ((nw == 8 || ring4) ? (size_t)4 * cob * wpl * 1024 : 0);
-    fill_divisors(s);
-#define PP_SPLIT_LAUNCH_H(T_, NS_, NW_, R4_, H_)                                                                        \
-    do {                                                                                                                \
-        static PpPerDeviceOnce once;                                                                                     \
-        once.run([] {     /* > 64 KB of dynamic LDS has to be allowed per kernel */                         \
-            (void)hipFuncSetAttribute((const void*)conv_split_kernel<T_, NS_, 2, 2, NW_, R4_, H_>, hipFuncAttributeMaxDynamicSharedMemorySize, (NW_ == 8 ? 160 : 100) * 1024); \
-            (void)hipFuncSetAttribute((const void*)conv_split_kernel<T_, NS_, 1, 2, NW_, R4_, H_>, hipFuncAttributeMaxDynamicSharedMemorySize, (NW_ == 8 ? 160 : 100) * 1024); \
-        });                                                                                                             \
-        if (cob == 2)                                                                                                   \
-            hipLaunchKernelGGL((conv_split_kernel<T_, NS_, 2, 2, NW_, R4_, H_>), grid, dim3(64 * NW_), lds, stream, s); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((conv_split_kernel<T_, NS_, 1, 2, NW_, R4_, H_>), grid, dim3(64 * NW_), lds, stream, s); \
-    } while (0)
-#define PP_SPLIT_LAUNCH_WIDE(NS_, COB_)                                                                                 \
-    do {                                                                                                                \
-        static PpPerDeviceOnce once;                                                                                     \
-        once.run([] {                                                                                       \
-            (void)hipFuncSetAttribute((const void*)conv_split_kernel<9, NS_, COB_, 2, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-        });                                                                                                             \
-        hipLaunchKernelGGL((conv_split_kernel<9, NS_, COB_, 2, 4, true, true>), grid, dim3(256), lds, stream, s);       \
-    } while (0)
-#define PP_SPLIT_LAUNCH(T_, NS_, NW_, R4_)                                                                              \
-    do {                                                                                                                \
-        if (f16) PP_SPLIT_LAUNCH_H(T_, NS_, NW_, R4_, true);                                                            \
-        else PP_SPLIT_LAUNCH_H(T_, NS_, NW_, R4_, false);                                                               \
-    } while (0)
-    if (mode == MODE_GEMM)
-        PP_SPLIT_LAUNCH(1, 4, 4, false);
-    else if (nw == 8) {
-        if (nslot <= 5) PP_SPLIT_LAUNCH(9, 5, 8, false);
-        else PP_SPLIT_LAUNCH(9, 6, 8, false);
-    } else if (ring4 && cob == 3) {
-        if (nslot <= 5) PP_SPLIT_LAUNCH_WIDE(5, 3);
-        else if (nslot == 6) PP_SPLIT_LAUNCH_WIDE(6, 3);
-        else if (nslot == 7) PP_SPLIT_LAUNCH_WIDE(7, 3);
-        else PP_SPLIT_LAUNCH_WIDE(8, 3);
-    } else if (ring4 && cob == 4) {
-        if (nslot <= 5) PP_SPLIT_LAUNCH_WIDE(5, 4);
-        else if (nslot == 6) PP_SPLIT_LAUNCH_WIDE(6, 4);
-        else if (nslot == 7) PP_SPLIT_LAUNCH_WIDE(7, 4);
-        else PP_SPLIT_LAUNCH_WIDE(8, 4);
-    } else if (ring4) {
-        if (nslot <= 5) PP_SPLIT_LAUNCH(9, 5, 4, true);
-        else if (nslot == 6) PP_SPLIT_LAUNCH(9, 6, 4, true);
-        else if (nslot == 7) PP_SPLIT_LAUNCH(9, 7, 4, true);
-        else PP_SPLIT_LAUNCH(9, 8, 4, true);
-    } else if (nslot <= 5)
-        PP_SPLIT_LAUNCH(9, 5, 4, false);
-    else if (nslot == 6)
-        PP_SPLIT_LAUNCH(9, 6, 4, false);
-    else if (nslot == 7)
-        PP_SPLIT_LAUNCH(9, 7, 4, false);
-    else
-        PP_SPLIT_LAUNCH(9, 8, 4, false);
-    PP_TL_END(mode == MODE_GEMM ? "gemm4" : nw == 8 ? "nw8" : ring4 ? "ring4" : "nw4", grid.x * grid.y);
+    PP_TL_END(tag, grid.x * grid.y);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        pp_set_error("conv_split launch failed: %s", hipGetErrorString(e));
+        pp_set_error("conv_split (%s) launch failed: %s", tag, hipGetErrorString(e));
         return PP_ERR_HIP;
     }
     return PP_OK;

@@ -124,21 +124,54 @@ struct ConvArgs {
     // builds a temporary copy when it picks the split kernel (single-op API; never under graph capture)
     const void* wsplit;
     // 0: single-op API -- the process-wide setting (pp_conv_exact) decides; 1 / 2: an op of a net created exact / split (ABI 7: a
-    // net's numerics never change after creation; with 2 the split kernel runs exactly where the net built split weights)
+    // net's numerics never change after creation; with 2 the split kernel runs exactly where the net planned it, SplitPlan)
     int numerics;
-    // split kernels: 0 = three bf16 planes, six products; 1 = the fp16 form (two activation planes, three products; round 5).  Fixed
-    // with the split weights (pp_conv_split_bytes / _weights / pp_launch_conv_split must see the same value)
+    // split kernels: 0 = three bf16 planes, six products; 1 = the fp16 form (two activation planes, three products; round 5).  An
+    // input of pp_conv_split_plan, which fixes the form of the split weights and of the kernel that reads them (SplitPlan::f16)
     int split_f16;
     // fp16 form: per-sample running maximum of |x| (pp_amax.h; required by the fp16 kernels) and, any conv kernel, where to fold max |y|
     // per sample of what this launch stores (null: nobody needs it).  Device pointers to N slots each.
     const unsigned* x_amax;
     unsigned* y_amax;
 };
-// fp32 convolution on the bf16 matrix cores (three-way split, six products; conv_split.hip)
-bool pp_conv_split_eligible(const ConvArgs& a);
-size_t pp_conv_split_bytes(const ConvArgs& a);
-int pp_conv_split_weights(const ConvArgs& a, void* out, hipStream_t stream);
-int pp_launch_conv_split(const ConvArgs& a, hipStream_t stream);   // `a` as prepared by pp_launch_conv, a.wsplit set
+// ---- fp32 convolution on the bf16 matrix cores (three-way split; conv_split.hip) ----------------------------------------------
+// pixel tiling of a split tap kernel: output tiles of TH x TW (MODE_TILE), the padded input as one stream (MODE_STREAM) or 256 output
+// pixels per workgroup (MODE_GEMM); eff: the fraction of a tile's pixels that are outputs (pick_tile / pick_tile_s2), < 0: none fits
+struct TileGeom {
+    int TH, TW, bw_log2, gx_log2, PWp, NP, NPp, tiles_x, tiles_y;
+    double eff;
+    int mode;
+};
+enum SplitKernel {
+    SPLIT_NONE = 0,       // not eligible: the float32-MFMA kernels
+    SPLIT_STEM7,          // ResNet-50's 7x7 / stride-2 stem, conv_split_stem7_kernel (fp16 form)
+    SPLIT_PRODUCT,        // 1x1 / full-cover layers on the product kernel conv_split_gemm_kernel (256 x 128 tiles)
+    SPLIT_C48,            // 3x3 / stride 1 with 33 .. 48 output channels, conv_split48_kernel
+    SPLIT_TAP3,           // 3x3 / stride 1 on the tap kernel conv_split_kernel, tile or stream
+    SPLIT_S2P,            // 3x3 / stride 2 on the tap kernel's strided-patch form
+    SPLIT_ONE_TAP,        // 1x1 / full-cover layers on the tap kernel's product form
+    SPLIT_TAP_GATHER,     // 3x3 / stride 2 on the tap kernel's product form, one step per (channel chunk, tap)
+};
+// How one conv layer runs on the split kernels.  pp_conv_split_plan decides it ONCE, from the layer's shape, its split form
+// (ConvArgs::split_f16) and the selection knobs -- never from the batch: whether the layer is eligible, the kernel, the layout and
+// size of its split weights and the tiling of its map.  A net plans each conv op at creation, together with its split weights, and
+// the weight split and every launch of the op read that plan, so the kernel reads the fragments in the layout they were built in.
+// What depends on the batch or on launch-time knobs (grid, the 8-wave form, channel blocks per wave, column order, the 4 GiB cut)
+// stays with pp_launch_conv_split.
+struct SplitPlan {
+    int kernel = SPLIT_NONE;
+    int f16 = 0;                // the split form of the weights and of the kernel
+    int taps = 1, cin = 0;      // taps (9 / 1) and channels per tap (a full-cover 'valid' conv is a 1x1 over KH * KW * Cin)
+    int ncb = 0;                // channel blocks of the split weights: 32 channels (SPLIT_C48: 16, whole columns of 3)
+    int nout = 0;               // fp16 form: output channels of the scale block behind the fragments (1 / c, then max |w|)
+    size_t frag_bytes = 0;      // the fragments (+ one spare step: the kernels fetch one step ahead) ...
+    size_t bytes = 0;           // ... and the whole split copy
+    TileGeom tile[2] = {};      // tap kernels: the map's tiling for 4 / 8 waves; strided patch: [0]
+    long long off = -1;         // an op of a net: byte offset of its split copy in pp_net::wsplit
+};
+SplitPlan pp_conv_split_plan(const ConvArgs& a);
+int pp_conv_split_weights(const SplitPlan& p, const ConvArgs& a, void* out, hipStream_t stream);
+int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stream);   // `a` as prepared by pp_launch_conv, a.wsplit set
 // true: the kernel this layer runs on folds max |y| per sample into ConvArgs::y_amax in its epilogue (pp_amax.h) -- the split
 // kernels always, the float32 kernels in their plain NHWC epilogue; false: the caller takes the maximum in a pass of its own
 bool pp_conv_tracks_amax(const ConvArgs& a, bool split);
@@ -147,7 +180,8 @@ bool pp_conv_split_f16_default();   // the process-wide default split form (pp_c
 // builds (and caches per device) the tap tables the pipelined kernel may use for this geometry; call outside graph capture
 int pp_conv_prepare(const ConvArgs& a);
 int pp_conv_out_dim(int in, int k, int stride, int pad, int dil);
-int pp_launch_conv(const ConvArgs& a, hipStream_t stream);
+// plan: an op of a net, the split plan it was created with; null: single-op API (the process-wide setting, planned per call)
+int pp_launch_conv(const ConvArgs& a, const SplitPlan* plan, hipStream_t stream);
 // software-pipelined variant (conv_igemm_p3.hip): same results; `a` as prepared by pp_launch_conv
 int pp_launch_conv_p3(const ConvArgs& a, int ct, int pt, hipStream_t stream, bool fake_addresses = false);
 
