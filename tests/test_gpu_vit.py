@@ -57,7 +57,7 @@ def _close_bf16(got_bits, ref_f32, ulps=1.0):
     (300, 256, 192, 0, True, 0, 0),          # ragged M (tail rows masked)
     (384, 384, 1280, 1, False, 0, 1),        # GELU, bf16 out
     (576, 1280, 640, 0, True, 192, 0),       # residual broadcast over row % 192 (position embedding form)
-    (1100, 640, 2560, 0, True, 0, 0),        # in-place residual stream form, ragged 256-row tiles
+    (1100, 640, 2560, 0, True, 0, 0),        # fc2 shape with a SEPARATE residual, ragged 256-row tiles (in place, C == res: test_gpu_vit_exact.py)
     (256, 256, 128, 0, False, 0, 0),         # N % 256 == 0 and K % 128 == 0: the shapes the ping-pong form (10, the default there) takes; 2 K tiles
     (300, 512, 256, 0, True, 0, 0),          # ... ragged M
     (640, 512, 1280, 1, False, 0, 1),        # ... GELU, bf16 out
