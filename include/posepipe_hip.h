@@ -560,11 +560,28 @@ int pp_reid_patches(pp_ctx* ctx, const uint8_t* frames, int n_frames, int src_h,
  * Replaces VideoPose3D TemporalModelOptimized1f + ChunkedGenerator windows reached from
  * wrappers/videopose3d.py:66-85, computed in the equivalent whole-clip dilated form.
  * net: a program built for the dilated form (posepipeline_amd.models.videopose3d).
- * in_buf is [1][T + 2*pad][>= in_features], out_buf [1][T][out_features]: the clip is processed in
- * chunks of T frames with a pad-frame halo, clamped to the clip (= np.pad mode 'edge').
- * kpts2d_norm: host [n_frames][in_features = 17*2] fp32 already screen-normalised
- * (videopose3d.py:26-37); out: host [n_frames][out_features = 17*3] fp32.
+ * in_buf is [1][T + 2*pad][>= in_features], out_buf [1][T][out_features].
+ *
+ * pp_videopose3d_lift_many lifts n_segs tracks ("segments") in one call.  kpts2d_norm is the packed
+ * [sum seg_frames[i]][in_features = 17*2] fp32 array of the tracks, segment after segment, already
+ * screen-normalised (videopose3d.py:26-37); seg_frames: host [n_segs], frames per segment, each >= 0;
+ * out: packed [sum seg_frames[i]][out_features = 17*3] fp32 in the same row order.
+ *   - Every segment is processed in chunks of T frames with a pad-frame halo.  The halo is clamped to
+ *     the SEGMENT, not to the packed array (= np.pad mode 'edge' on that track alone): segment i of
+ *     `out` is exactly what a call with segment i alone returns.  A segment of 0 frames contributes no
+ *     rows; n_segs == 0 or only empty segments: PP_OK, the device is not touched.
+ *   - A work item is one (segment, chunk) pair and occupies ONE batch sample, [T + 2*pad][channels]
+ *     with the channels >= in_features zero.  Work items of different segments share a batch, in
+ *     groups of at most the net's max_batch.  What a sample holds does not depend on the grouping.
+ *   - mem = PP_MEM_HOST: kpts2d_norm and out are host arrays; one upload, one download.
+ *     mem = PP_MEM_DEVICE: both are device arrays that do not overlap; nothing is copied but the work
+ *     table.  Either way everything is queued on the context's stream and the call returns after ONE
+ *     stream synchronisation: the results are complete on return.
+ * pp_videopose3d_lift is the case n_segs = 1, seg_frames = {n_frames}, PP_MEM_HOST.
  */
+int pp_videopose3d_lift_many(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm,
+                             const int32_t* seg_frames, int n_segs, int in_features, int out_features,
+                             int pad, float* out, int mem);
 int pp_videopose3d_lift(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, int n_frames,
                         int in_features, int out_features, int pad, float* out);
 

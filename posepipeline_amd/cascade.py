@@ -29,7 +29,7 @@ from .models import videopose3d as vp3d
 from .person_stream import FILL_LIMIT, PersonStreams, collect  # noqa: F401  (collect: re-exported for callers)
 from .program import Net
 from .tracking import Tracker
-from .wrappers.videopose3d import lift
+from .wrappers.videopose3d import lift, lift_many
 
 
 # Default certification thresholds of Cascade(id_numerics="certified"): 4x the largest deviation between the fp16-form and the
@@ -58,7 +58,8 @@ class Cascade:
     def __init__(self, ctx: L.Context, det_sd, pose_sd: dict, lift_sd: dict, src_h: int, src_w: int,
                  chunk: int = 8, max_persons: int = 1, pose_spec=None, post="unbiased", blur_kernel=17,
                  tracking: str = "MMTrack_deepsort", keep_tracks=None, flip_pairs=None, blob_fn=None, reid_sd=None,
-                 overlap_detector: bool | None = None, numerics=None, id_numerics=None, certify_eps=None, det_lanes=None, pose_lanes=None):
+                 overlap_detector: bool | None = None, numerics=None, id_numerics=None, certify_eps=None, det_lanes=None, pose_lanes=None,
+                 batched_lift: bool = True):
         """blob_fn(name, program) -> (device pointer, n_floats) or None, name in "det_a", "det_b", "pose", "lift" (called in
         that order): a weight blob that is already resident on the device -- parallel.broadcast_blob_device delivers rank
         0's over RCCL; the *_sd arguments then only define the program structure (ops, buffers, blob offsets).
@@ -67,7 +68,10 @@ class Cascade:
         asynchronous, no thread); the next step collects it.  "pipeline": the same on the cascade's one stream; False / "off": none.
         Results are unchanged (same kernels, same order per stage).  Not with the ReID branch (it reads the detector's resident input
         tensor of the CURRENT chunk) nor with certified ids (synchronous passes).  POSEPIPE_OVERLAP_DETECTOR=0 / 1 / 3 overrides
-        (off / stream / pipeline)."""
+        (off / stream / pipeline).
+        batched_lift: True (default): the lifting ranges of every followed person that become computable in a step go through ONE
+        device-side call (pp_videopose3d_lift_many: their chunks share the lifting program's batch); False: one single-track call per
+        person, one after the other.  Results are bit-equal (a batch sample holds the same values either way)."""
         # numerics: "exact" / "split" / None (= the process default at this moment) for EVERY program this cascade creates, passed
         # down explicitly -- two threads building cascades in different modes do not interfere (unlike _lib.default_numerics).
         # id_numerics (round 5): numerics of the programs whose outputs feed INTEGER decisions -- the detector (top-k, NMS, score
@@ -93,6 +97,7 @@ class Cascade:
         self.max_persons = max_persons
         self.tracking = tracking
         self.keep_tracks = keep_tracks
+        self.batched_lift = bool(batched_lift)
         blob_fn = blob_fn or (lambda name, prog: None)
         self.reid = None
         if tracking == "DeepSortYOLOv4":
@@ -211,7 +216,11 @@ class Cascade:
         # the lifting network takes the 17 COCO joints; wider heads (Halpe-136 / WholeBody-133) start with them
         self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs,
                                      lambda kn: lift(self.lift_net, self.lift_spec, kn[:, :17]),
-                                     max_persons=self.max_persons, keep_tracks=self.keep_tracks)
+                                     max_persons=self.max_persons, keep_tracks=self.keep_tracks,
+                                     lift_many_fn=self._lift_many if self.batched_lift else None)
+
+    def _lift_many(self, kns):
+        return lift_many(self.lift_net, self.lift_spec, [kn[:, :17] for kn in kns])
 
     @property
     def n_frames(self):

@@ -651,6 +651,13 @@ int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c) {
 int pp_net_max_batch(pp_net* net) { return net ? net->max_batch : 0; }
 pp_ctx* pp_net_ctx(pp_net* net) { return net ? net->ctx : nullptr; }
 
+// the caller's own kernel has just overwritten `buf`: a pending promise of its maxima (pp_net_input_amax) is void
+void pp_net_void_input_amax(pp_net* net, int buf) {
+    if (!net) return;
+    for (auto& e : net->ext)
+        if (e.buf == buf) e.provided = false;
+}
+
 unsigned* pp_net_input_amax_slot(pp_net* net, int buf) {
     if (!net || !net->amax) return nullptr;
     for (auto& e : net->ext)
@@ -970,8 +977,7 @@ int pp_net_forward(pp_net* net, int batch, int in_buf, const float* in, int out_
     const hipMemcpyKind kin = mem == PP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     const hipMemcpyKind kout = mem == PP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     PP_HIP_CHECK(hipMemcpyAsync(net->buf_ptr(in_buf), in, (size_t)batch * net->buf_elems[in_buf] * sizeof(float), kin, s));
-    for (auto& e : net->ext)      // the input was just overwritten here: a pending promise of maxima (pp_net_input_amax) is void
-        if (e.buf == in_buf) e.provided = false;
+    pp_net_void_input_amax(net, in_buf);      // the input was just overwritten here
     int rc = pp_net_run(net, batch, 0, (int)net->ops.size());
     if (rc != PP_OK) return rc;
     PP_HIP_CHECK(hipMemcpyAsync(out, net->buf_ptr(out_buf), (size_t)batch * net->buf_elems[out_buf] * sizeof(float), kout, s));

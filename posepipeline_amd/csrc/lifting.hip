@@ -1,55 +1,163 @@
-// pp_videopose3d_lift: 2D -> 3D temporal lifting of one keypoint track in the whole-clip dilated form.
+// pp_videopose3d_lift_many / pp_videopose3d_lift: 2D -> 3D temporal lifting of keypoint tracks in the whole-clip dilated form.
 //
 // Replaces the per-window loop of pose_pipeline/wrappers/videopose3d.py:66-85: ChunkedGenerator builds
 // one edge-replicated 243-frame window per output frame and TemporalModelOptimized1f (strided convs)
-// reduces each to one frame -- 10.4x redundant.  Here the clip is cut into chunks of T output frames;
-// each chunk reads its frames plus a `pad`-frame halo (clamped to the clip = edge replication) and the
-// dilated program (posepipeline_amd/models/videopose3d.py, dilations 1,3,9,27,81) produces all T
+// reduces each to one frame -- 10.4x redundant.  Here every track (segment) is cut into chunks of T output
+// frames; each chunk reads its frames plus a `pad`-frame halo (clamped to the SEGMENT = edge replication) and
+// the dilated program (posepipeline_amd/models/videopose3d.py, dilations 1,3,9,27,81) produces all T
 // frames at once.  Same weights, same taps per output in the same (tap, channel) order, hence
 // bit-identical to the strided form (oracle/nets.py VideoPose3DRef).
+//
+// A work item is one (segment, chunk) pair and occupies one batch sample; items of different segments share a
+// batch.  The windows are assembled on the device: lift_gather_kernel writes the program's input buffer from the
+// packed tracks, lift_scatter_kernel copies the valid rows of the output buffer into the packed result.  A call
+// uploads the tracks and a small work table once, queues (gather, program, scatter) per batch group, downloads
+// once and synchronises once.  pp_videopose3d_lift is the one-segment, host-memory case of the same code.
 #include "pp_internal.h"
+
+#include <climits>
 
 int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
 int pp_net_max_batch(pp_net* net);
 pp_ctx* pp_net_ctx(pp_net* net);
+void pp_net_void_input_amax(pp_net* net, int buf);
+
+namespace {
+
+// per work item: first row of its segment in the packed arrays, rows of the segment, first output frame of the chunk
+struct LiftItem {
+    int32_t base, len, t0;
+};
+
+// in[ci][j][c] = c < in_features ? src[base + clamp(t0 - pad + j, 0, len - 1)][c] : 0, for the items of one batch group.
+// V = float2 when both channel counts are even (34 -> 36 floats = 17 -> 18 float2), else float; the counts are in units of V.
+template <class V>
+__global__ void lift_gather_kernel(const V* __restrict__ src, const LiftItem* __restrict__ items, int total, int iw, int ic,
+                                   int in_features, int pad, V* __restrict__ in) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int c = idx % ic;
+    const int j = (idx / ic) % iw;
+    const LiftItem it = items[idx / (ic * iw)];
+    V v{};
+    if (c < in_features) {
+        int row = it.t0 - pad + j;                          // np.pad(..., 'edge') == clamp, inside the segment
+        row = row < 0 ? 0 : (row >= it.len ? it.len - 1 : row);
+        v = src[((size_t)it.base + row) * in_features + c];
+    }
+    in[idx] = v;
+}
+
+// dst[base + t0 + r][c] = out[ci][r][c] for r < min(T, len - t0): per item one contiguous run of floats
+__global__ void lift_scatter_kernel(const float* __restrict__ out, const LiftItem* __restrict__ items, int total, int T, int oc,
+                                    float* __restrict__ dst) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int e = idx % (T * oc);
+    const LiftItem it = items[idx / (T * oc)];
+    const int cnt = min(T, it.len - it.t0);
+    if (e < cnt * oc) dst[((size_t)it.base + it.t0) * oc + e] = out[idx];
+}
+
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// everything of one call up to, not including, the final synchronisation; `items` must outlive that synchronisation
+int lift_many_enqueue(pp_net* net, pp_ctx* ctx, int in_buf, int out_buf, const float* kpts2d_norm, const std::vector<LiftItem>& items,
+                      size_t rows, int in_features, int pad, int iw, int ic, int T, int oc, float* out, int mem) {
+    hipStream_t s = ctx->stream;
+    const int max_b = pp_net_max_batch(net);
+    const bool host = mem == PP_MEM_HOST;
+    const size_t in_e = rows * in_features, out_e = rows * oc;
+    int rc = ctx->ensure_scratch(ScratchCursor::align(items.size() * sizeof(LiftItem)) +
+                                 (host ? ScratchCursor::align(in_e * sizeof(float)) + ScratchCursor::align(out_e * sizeof(float)) : 0));
+    if (rc != PP_OK) return rc;
+    ScratchCursor cur(ctx);
+    LiftItem* d_items = cur.take<LiftItem>(items.size());
+    const float* d_src = kpts2d_norm;
+    float* d_dst = out;
+    if (host) {
+        float* staged = cur.take<float>(in_e);
+        d_dst = cur.take<float>(out_e);
+        PP_HIP_CHECK(hipMemcpyAsync(staged, kpts2d_norm, in_e * sizeof(float), hipMemcpyHostToDevice, s));
+        d_src = staged;
+    }
+    PP_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(LiftItem), hipMemcpyHostToDevice, s));
+    void *in_ptr = nullptr, *out_ptr = nullptr;
+    rc = pp_net_buffer(net, in_buf, &in_ptr, nullptr);
+    if (rc == PP_OK) rc = pp_net_buffer(net, out_buf, &out_ptr, nullptr);
+    if (rc != PP_OK) return rc;
+    const bool vec2 = in_features % 2 == 0 && ic % 2 == 0 && aligned8(d_src) && aligned8(in_ptr);
+    const int n_items = (int)items.size();
+    for (int c0 = 0; c0 < n_items; c0 += max_b) {
+        const int b = std::min(max_b, n_items - c0);
+        if (vec2) {
+            const int total = b * iw * (ic / 2);
+            hipLaunchKernelGGL(lift_gather_kernel<float2>, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(d_src),
+                               d_items + c0, total, iw, ic / 2, in_features / 2, pad, static_cast<float2*>(in_ptr));
+        } else {
+            const int total = b * iw * ic;
+            hipLaunchKernelGGL(lift_gather_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, s, d_src, d_items + c0, total, iw, ic,
+                               in_features, pad, static_cast<float*>(in_ptr));
+        }
+        PP_HIP_CHECK(hipGetLastError());
+        pp_net_void_input_amax(net, in_buf);      // the input was just overwritten here, not by pp_net_forward
+        rc = pp_net_run(net, b, 0, -1);
+        if (rc != PP_OK) return rc;
+        const int total = b * T * oc;
+        hipLaunchKernelGGL(lift_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, s, static_cast<const float*>(out_ptr), d_items + c0,
+                           total, T, oc, d_dst);
+        PP_HIP_CHECK(hipGetLastError());
+    }
+    if (host) PP_HIP_CHECK(hipMemcpyAsync(out, d_dst, out_e * sizeof(float), hipMemcpyDeviceToHost, s));
+    return PP_OK;
+}
+
+// `who`: the entry point the caller used, for the messages
+int lift_many(const char* who, pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, const int32_t* seg_frames, int n_segs,
+              int in_features, int out_features, int pad, float* out, int mem) {
+    PP_REQUIRE(net && kpts2d_norm && seg_frames && out, "%s: NULL argument", who);
+    PP_REQUIRE(n_segs >= 0 && in_features > 0 && out_features > 0 && pad >= 0, "%s: bad dims", who);
+    PP_REQUIRE(mem == PP_MEM_HOST || mem == PP_MEM_DEVICE, "%s: mem %d is neither PP_MEM_HOST nor PP_MEM_DEVICE", who, mem);
+    size_t rows = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        PP_REQUIRE(seg_frames[i] >= 0, "%s: bad dims (segment %d has %d frames)", who, i, seg_frames[i]);
+        rows += (size_t)seg_frames[i];
+    }
+    PP_REQUIRE(rows <= (size_t)INT_MAX, "%s: %zu frames in one call (the work table holds int32 rows)", who, rows);
+    if (rows == 0) return PP_OK;
+    int ih, iw, ic, oh, ow, oc;
+    PP_REQUIRE(pp_net_dims(net, in_buf, &ih, &iw, &ic) == PP_OK && pp_net_dims(net, out_buf, &oh, &ow, &oc) == PP_OK,
+               "%s: bad buffer id", who);
+    PP_REQUIRE(ih == 1 && oh == 1 && ic >= in_features && oc == out_features && iw == ow + 2 * pad,
+               "%s: program shape (in %dx%dx%d, out %dx%dx%d) does not match pad=%d / features %d->%d",
+               who, ih, iw, ic, oh, ow, oc, pad, in_features, out_features);
+    const int T = ow;
+    std::vector<LiftItem> items;                  // one per (segment, chunk), segment after segment
+    int32_t base = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        for (int32_t t0 = 0; t0 < seg_frames[i]; t0 += T) items.push_back({base, seg_frames[i], t0});
+        base += seg_frames[i];
+    }
+    pp_ctx* ctx = pp_net_ctx(net);
+    PpRange range("pp_videopose3d_lift_many");
+    int rc = lift_many_enqueue(net, ctx, in_buf, out_buf, kpts2d_norm, items, rows, in_features, pad, iw, ic, T, oc, out, mem);
+    // one synchronisation per call, also after an error: `items` and the caller's host arrays are read by queued copies
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc != PP_OK) return rc;
+    PP_HIP_CHECK(e);
+    return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_videopose3d_lift_many(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, const int32_t* seg_frames,
+                                        int n_segs, int in_features, int out_features, int pad, float* out, int mem) {
+    return lift_many("pp_videopose3d_lift_many", net, in_buf, out_buf, kpts2d_norm, seg_frames, n_segs, in_features, out_features, pad,
+                     out, mem);
+}
 
 extern "C" int pp_videopose3d_lift(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, int n_frames,
                                    int in_features, int out_features, int pad, float* out) {
-    PP_REQUIRE(net && kpts2d_norm && out, "pp_videopose3d_lift: NULL argument");
-    PP_REQUIRE(n_frames >= 0 && in_features > 0 && out_features > 0 && pad >= 0, "pp_videopose3d_lift: bad dims");
-    if (n_frames == 0) return PP_OK;
-    int ih, iw, ic, oh, ow, oc;
-    PP_REQUIRE(pp_net_dims(net, in_buf, &ih, &iw, &ic) == PP_OK && pp_net_dims(net, out_buf, &oh, &ow, &oc) == PP_OK,
-               "pp_videopose3d_lift: bad buffer id");
-    PP_REQUIRE(ih == 1 && oh == 1 && ic >= in_features && oc == out_features && iw == ow + 2 * pad,
-               "pp_videopose3d_lift: program shape (in %dx%dx%d, out %dx%dx%d) does not match pad=%d / features %d->%d",
-               ih, iw, ic, oh, ow, oc, pad, in_features, out_features);
-    pp_ctx* ctx = pp_net_ctx(net);
-    const int T = ow;
-    const int max_b = pp_net_max_batch(net);
-    const int n_chunks = (n_frames + T - 1) / T;
-    std::vector<float> hin, hout;
-    for (int c0 = 0; c0 < n_chunks; c0 += max_b) {
-        const int b = std::min(max_b, n_chunks - c0);
-        hin.assign((size_t)b * iw * ic, 0.f);
-        for (int ci = 0; ci < b; ++ci) {
-            const int t0 = (c0 + ci) * T;
-            for (int j = 0; j < iw; ++j) {
-                int src = t0 - pad + j;                       // np.pad(..., 'edge') == clamp
-                src = src < 0 ? 0 : (src >= n_frames ? n_frames - 1 : src);
-                memcpy(&hin[((size_t)ci * iw + j) * ic], kpts2d_norm + (size_t)src * in_features,
-                       (size_t)in_features * sizeof(float));
-            }
-        }
-        hout.resize((size_t)b * T * oc);
-        int rc = pp_net_forward(net, b, in_buf, hin.data(), out_buf, hout.data(), PP_MEM_HOST);
-        if (rc != PP_OK) return rc;
-        for (int ci = 0; ci < b; ++ci) {
-            const int t0 = (c0 + ci) * T;
-            const int cnt = std::min(T, n_frames - t0);
-            memcpy(out + (size_t)t0 * oc, &hout[(size_t)ci * T * oc], (size_t)cnt * oc * sizeof(float));
-        }
-    }
-    (void)ctx;
-    return PP_OK;
+    const int32_t seg = n_frames;
+    return lift_many("pp_videopose3d_lift", net, in_buf, out_buf, kpts2d_norm, &seg, 1, in_features, out_features, pad, out, PP_MEM_HOST);
 }

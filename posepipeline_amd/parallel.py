@@ -176,7 +176,7 @@ def _takes_need(fn) -> bool:
 
 
 def process_video_sharded(dist, n_frames, chunks_fn, detect_fn, associate_fn, topdown_fn, lift_fn, src_hw, device="cpu",
-                          num_joints=17, pad=121, max_persons=1, keep_tracks=None, timings=None):
+                          num_joints=17, pad=121, max_persons=1, keep_tracks=None, timings=None, lift_many_fn=None):
     """Run the cascade on frames [0, n_frames) sharded over the ranks of `dist` (rank r owns the contiguous frames
     [b_r, b_{r+1})).
 
@@ -192,6 +192,8 @@ def process_video_sharded(dist, n_frames, chunks_fn, detect_fn, associate_fn, to
     associate_fn(dets_all_frames)  -> per frame, tracker rows (track_id, x1, y1, x2, y2, score[, tlwh]); sequential
     topdown_fn(handle, n, idx, boxes) -> [len(idx)][K][3] key points of the person-frames (chunk-local frame idx, tlwh)
     lift_fn(kn)                    -> (m, J, 3) 3D joints of a normalised 2D context (m, K, 2)
+    lift_many_fn(kns)              -> optional: the same for a list of contexts in one call (wrappers.videopose3d.lift_many); when
+                                      given, every track is lifted by that one call and lift_fn is not used
     timings: optional dict that receives per-phase wall seconds of this rank.
 
     Both device passes advance in per-chunk ROUNDS: in round k every rank processes its k-th chunk and starts an asynchronous
@@ -329,7 +331,8 @@ def process_video_sharded(dist, n_frames, chunks_fn, detect_fn, associate_fn, to
         t_2d[1] += t_wait
         return out
 
-    ps = PersonStreams(num_joints, pad, src_hw, sharded_topdown, lift_fn, max_persons=max_persons, keep_tracks=keep_tracks)
+    ps = PersonStreams(num_joints, pad, src_hw, sharded_topdown, lift_fn, max_persons=max_persons, keep_tracks=keep_tracks,
+                       lift_many_fn=lift_many_fn)
     ps.ingest(tracks)
     out = ps.advance(final=True)        # lifting of every track, replicated (0.03 GFLOP per frame)
     t4 = time.perf_counter()

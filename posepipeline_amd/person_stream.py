@@ -25,6 +25,8 @@ differ by <= 1 float32 ulp of the normalised input).
 The compute stages are callables, so this module needs no GPU (tests/test_person_stream.py):
     topdown_fn(jobs)  jobs = [(track_id, frame, tlwh float64[4])] -> [len(jobs)][K][3] float32
     lift_fn(kn)       kn = (n, K, 2) normalised key points -> (n, J, 3)
+    lift_many_fn(kns) optional: kns = list of such contexts -> list of (n_i, J, 3), element i equal to lift_fn(kns[i]); when given,
+                      advance() makes ONE call with the contexts of every stream instead of one lift_fn call per stream
 """
 from __future__ import annotations
 
@@ -92,9 +94,10 @@ class PersonStreams:
     """max_persons: tracks followed at the same time (new ids are adopted, in row order, while fewer are live; an id that
     appears while max_persons others are live is never followed); keep_tracks: follow exactly these ids instead."""
 
-    def __init__(self, num_joints: int, pad: int, src_hw, topdown_fn, lift_fn, max_persons: int = 1, keep_tracks=None):
+    def __init__(self, num_joints: int, pad: int, src_hw, topdown_fn, lift_fn, max_persons: int = 1, keep_tracks=None,
+                 lift_many_fn=None):
         self.k, self.pad, self.src = int(num_joints), int(pad), tuple(src_hw)
-        self.topdown_fn, self.lift_fn = topdown_fn, lift_fn
+        self.topdown_fn, self.lift_fn, self.lift_many_fn = topdown_fn, lift_fn, lift_many_fn
         self.max_persons = max_persons
         self.keep_tracks = None if keep_tracks is None else set(int(k) for k in keep_tracks)
         self.n_frames = 0             # frames tracked so far
@@ -143,15 +146,19 @@ class PersonStreams:
                     st.last_raw = t
             self.n_frames += 1
 
-    def _lift_range(self, st: _PersonStream, lo: int, hi: int, n_total):
-        """3D of frames [lo, hi) of one stream from the context [lo - pad, hi + pad)"""
+    def _lift_context(self, st: _PersonStream, lo: int, hi: int, n_total):
+        """normalised 2D context [lo - pad, hi + pad) of one stream: what lifting frames [lo, hi) reads"""
         pad = self.pad
         zero = np.zeros((self.k, 3), np.float32)
         rows = [st.row(t, n_total) for t in range(lo - pad, hi + pad)]
         arr = np.stack([zero if r is None else r for r in rows])[:, :, :2]
         arr = arr.astype(np.float64) if st.any_absent else arr          # the reference's dtype-dependent normalisation
-        kn = normalize_screen_coordinates(arr, self.src[1], self.src[0])
-        out = self.lift_fn(kn)
+        return normalize_screen_coordinates(arr, self.src[1], self.src[0])
+
+    def _lift_range(self, st: _PersonStream, lo: int, hi: int, n_total):
+        """3D of frames [lo, hi) of one stream from the context [lo - pad, hi + pad)"""
+        pad = self.pad
+        out = self.lift_fn(self._lift_context(st, lo, hi, n_total))
         return out[pad:pad + hi - lo]
 
     def advance(self, final: bool = False):
@@ -171,6 +178,7 @@ class PersonStreams:
         kp, kp_frames, kp3, kp3_frames = {}, {}, {}, {}
         pad = self.pad
         zero = np.zeros((self.k, 3), np.float32)
+        batched = []                  # lift_many_fn: (track_id, frames lifted, context) of every range that became computable
         for tid in sorted(self.streams):
             st = self.streams[tid]
             ts = decided.get(tid, [])
@@ -195,7 +203,10 @@ class PersonStreams:
             else:
                 hi, n_total = st.next_dec - pad, None
             if hi > st.next3d:
-                kp3[tid] = self._lift_range(st, st.next3d, hi, n_total)
+                if self.lift_many_fn is None:
+                    kp3[tid] = self._lift_range(st, st.next3d, hi, n_total)
+                else:                 # the context is built here, from the rows the stream holds now; lifted below, all at once
+                    batched.append((tid, hi - st.next3d, self._lift_context(st, st.next3d, hi, n_total)))
                 kp3_frames[tid] = np.arange(st.next3d, hi, dtype=np.int64)
                 st.next3d = hi
             if final or ended:
@@ -206,6 +217,11 @@ class PersonStreams:
                 if drop > 0:
                     del st.k2[:drop]
                     st.k2_base += drop
+        if batched:
+            lifted = self.lift_many_fn([kn for _, _, kn in batched])
+            assert len(lifted) == len(batched), (len(lifted), len(batched))
+            for (tid, n, _), out in zip(batched, lifted):
+                kp3[tid] = out[pad:pad + n]
         return dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames)
 
 

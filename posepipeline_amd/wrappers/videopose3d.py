@@ -6,6 +6,7 @@ edge-replicated 243-frame window per frame (ChunkedGenerator, :66-75) and runs
 TemporalModelOptimized1f on the CPU in batches of `batch_size`; here the whole clip goes through the
 dilated program on the GPU (pp_videopose3d_lift), which evaluates the same sums.  `batch_size` and
 `transform_coco` are accepted and, like `transform_coco` in the reference, have no effect on the result.
+`lift_many` lifts several tracks in one device-side call (pp_videopose3d_lift_many); the cascade uses it.
 """
 from __future__ import annotations
 
@@ -61,6 +62,25 @@ def lift(net, spec, keypoints_norm: np.ndarray) -> np.ndarray:
                                                x.shape[1], spec.num_joints_out * 3, spec.pad, _lib.ptr(out)),
                "pp_videopose3d_lift")
     return out.reshape(n, spec.num_joints_out, 3)
+
+
+def lift_many(net, spec, kns) -> list:
+    """kns: list of (n_i, J, 2) normalised key points -> list of (n_i, J_out, 3) float32, via ONE pp_videopose3d_lift_many call: every
+    track's chunks share the net's batch.  Element i is bit-equal to lift(net, spec, kns[i])."""
+    xs = [np.ascontiguousarray(np.asarray(k).astype("float32")).reshape(len(k), int(np.prod(np.shape(k)[1:]))) for k in kns]
+    f_out = spec.num_joints_out * 3
+    if not xs:
+        return []
+    f_in = xs[0].shape[1]
+    assert all(x.shape[1] == f_in for x in xs), "lift_many: every track has the same joints"
+    seg = np.array([x.shape[0] for x in xs], np.int32)
+    packed = np.ascontiguousarray(np.concatenate(xs))
+    out = np.zeros((int(seg.sum()), f_out), np.float32)
+    _lib.check(net.ctx.lib.pp_videopose3d_lift_many(net.handle, net.prog.named["input"], net.prog.named["output"], _lib.ptr(packed),
+                                                    _lib.ptr(seg), len(seg), f_in, f_out, spec.pad, _lib.ptr(out), _lib.PP_MEM_HOST),
+               "pp_videopose3d_lift_many")
+    ends = np.cumsum(seg)
+    return [out[e - n:e].reshape(n, spec.num_joints_out, 3) for e, n in zip(ends, seg)]
 
 
 def process_videopose3d(key, batch_size=32, transform_coco=False):
