@@ -46,7 +46,8 @@ extern "C" {
                                  second form -- two float16 terms per operand, three products (conv_split.hip, round 5);
                                  pp_detector_constants
                               10: pp_detector_enable_margins / pp_detector_margins (per-frame decision margins of the detection path);
-                                 pp_net_input_amax is a one-shot promise */
+                                 pp_net_input_amax is a one-shot promise; PP_OP_BILINEAR_ADD (an added op type over existing pp_op
+                                 fields: no struct or signature changed, so the version stays 10) */
 
 typedef enum {
     PP_OK = 0,
@@ -141,6 +142,14 @@ typedef enum {
                                 + in3[y >> up3_log2][x >> up3_log2]) + res2[y][x]): nearest upsample + accumulate of an HRNet
                                 fuse layer in mmpose's summation order (res1, in2, in3, res2 optional; relu: PP_RELU_NONE /
                                 PP_RELU_LAST); same additions, same order as a chain of convs with up_log2, in one pass */
+    PP_OP_BILINEAR_ADD = 10, /* out[y][x][out_c_off + c] = act(((res1[y][x][c] + B(in)) + B(in2)) + B(in3)), B = bilinear upsampling by
+                                2^up_log2 / 2^up2_log2 / 2^up3_log2 with half-pixel centres (F.interpolate(mode='bilinear',
+                                align_corners=False)): sy = max((y + 0.5) / s - 0.5, 0), y0 = floor(sy), y1 = min(y0 + 1, h - 1), ly1 = sy -
+                                y0, ly0 = 1 - ly1 (the same in x); B = ly0 * (lx0 * a00 + lx1 * a01) + ly1 * (lx0 * a10 + lx1 * a11), every
+                                product and sum rounded to float32 (no FMA).  The fuse layers of HRNetv2 (res1, in2, in3 optional; relu:
+                                PP_RELU_NONE / PP_RELU_LAST) and, with out_c_off, the resize + concatenate in front of its head: channels
+                                [out_c_off, out_c_off + cout) of a wider NHWC `out`, the others untouched.  cin == cout, % 4 == 0.
+                                Uses existing pp_op fields only: sizeof(pp_op) and PP_ABI_VERSION are unchanged */
 } pp_op_type;
 
 #define PP_RELU_NONE 0
@@ -171,7 +180,7 @@ typedef struct pp_op {
                                  bit 2 / 3: pad_h / pad_w apply in front only: the last output row / column of the
                                  symmetric-padding result is not computed (the 2x2 sub-convolutions of a deconvolution) */
     int64_t w_off, b_off;     /* float offsets into the weight blob: W (layout below), bias[cout_pad16] */
-    /* ABI 7 -- PP_OP_UPSAMPLE_ADD only (every other op: -1 / 0): two more coarse inputs, so that a whole HRNet fuse sum
+    /* ABI 7 -- PP_OP_UPSAMPLE_ADD and PP_OP_BILINEAR_ADD only (every other op: -1 / 0): two more coarse inputs, so that a whole HRNet fuse sum
      * y_i = relu(((partial + up(t_a)) + up(t_b)) + up(t_c)) is ONE pass over the fine map (mmpose's `y += ...` order) */
     int32_t in2, in3;         /* buffer ids, -1 = none */
     int32_t up2_log2, up3_log2;

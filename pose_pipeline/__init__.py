@@ -3,17 +3,20 @@
 The reference's make() methods import the wrappers by these paths (pose_pipeline/pipeline.py:525-547 `from
 pose_pipeline.wrappers.mmtrack import mmtrack_bounding_boxes`, :1020-1039 `...wrappers.mmpose import
 mmpose_top_down_person`, :1270-1273 `...wrappers.videopose3d import process_videopose3d`, :519-523
-`...wrappers.deep_sort_yolov4.parser import tracking_bounding_boxes`), and scripts use `from pose_pipeline import *` and
+`...wrappers.deep_sort_yolov4.parser import tracking_bounding_boxes`, :2012-2018 `...wrappers.hand_bbox`, :2124-2139
+`...wrappers.hand_estimation`), and scripts use `from pose_pipeline import *` and
 `pose_pipeline.utils.standard_pipelines`.  Putting this directory (the repository root) on sys.path BEFORE a reference
 checkout makes every one of those imports land on the drop-in, with no edit to the caller.
 Each sub-module below replaces itself in sys.modules with the posepipeline_amd module of the same role, so
 `pose_pipeline.wrappers.mmpose is posepipeline_amd.wrappers.mmpose` (one module object, one model cache).
-Only the hot-path modules exist here; everything else of the reference (SMPL, OpenPose, hand / face wrappers ...) is out
+Only the hot-path modules exist here; everything else of the reference (SMPL, OpenPose, face wrappers ...) is out
 of scope and raises ImportError as an absent module should.
 """
 import os
 
-from posepipeline_amd.pipeline import (BestDetectedFrames, DetectedFrames, LiftingMethod, LiftingMethodLookup,  # noqa: F401
+from posepipeline_amd.pipeline import (BestDetectedFrames, DetectedFrames, HandBbox, HandBboxMethod,  # noqa: F401
+                                       HandBboxMethodLookup, HandPoseEstimation, HandPoseEstimationMethod,
+                                       HandPoseEstimationMethodLookup, LiftingMethod, LiftingMethodLookup,
                                        LiftingPerson, PersonBbox, PersonBboxValid, TopDownMethod, TopDownMethodLookup,
                                        TopDownPerson, TrackingBbox, TrackingBboxMethod, TrackingBboxMethodLookup, Video,
                                        VideoInfo)
@@ -29,5 +32,6 @@ MODEL_DATA_DIR = _model_data_dir()
 
 __all__ = ["Video", "VideoInfo", "TrackingBboxMethodLookup", "TrackingBboxMethod", "TrackingBbox", "PersonBboxValid",
            "PersonBbox", "DetectedFrames", "BestDetectedFrames", "TopDownMethodLookup", "TopDownMethod", "TopDownPerson", "LiftingMethodLookup",
-           "LiftingMethod", "LiftingPerson", "MODEL_DATA_DIR", "add_path", "set_environmental_variables",
+           "LiftingMethod", "LiftingPerson", "HandBboxMethodLookup", "HandBboxMethod", "HandBbox", "HandPoseEstimationMethodLookup",
+           "HandPoseEstimationMethod", "HandPoseEstimation", "MODEL_DATA_DIR", "add_path", "set_environmental_variables",
            "pytorch_memory_limit", "tensorflow_memory_limit"]

@@ -18,6 +18,7 @@ PP_MEM_HOST, PP_MEM_DEVICE = 0, 1
 PP_OP_CONV, PP_OP_MAXPOOL, PP_OP_ROIALIGN, PP_OP_COPY, PP_OP_VIT_ENCODER, PP_OP_DEPTH_TO_SPACE, PP_OP_UPSAMPLE_ADD = 1, 2, 3, 4, 5, 6, 7
 PP_OP_DECONV_BF16 = 8
 PP_OP_AVGPOOL = 9
+PP_OP_BILINEAR_ADD = 10
 PP_RELU_NONE, PP_RELU_LAST, PP_RELU_FIRST = 0, 1, 2
 PP_ACT_LEAKY, PP_ACT_MISH, PP_ACT_ELU, PP_ACT_SWISH = 3, 4, 5, 6
 PP_NET_NUMERICS_DEFAULT, PP_NET_NUMERICS_EXACT, PP_NET_NUMERICS_SPLIT = 0, 1, 2

@@ -314,10 +314,10 @@ static void net_plan_amax(pp_net* net) {
     net->ext.clear();
     if (net->numerics != PP_NET_NUMERICS_SPLIT || !net->split_f16) return;
     auto is_h = [&](int i) { return net->ops[i].type == PP_OP_CONV && net->split_plan[i].kernel != SPLIT_NONE; };
-    // producers with a fused maximum: convolutions (pp_conv_tracks_amax) and PP_OP_UPSAMPLE_ADD
+    // producers with a fused maximum: convolutions (pp_conv_tracks_amax), PP_OP_UPSAMPLE_ADD and PP_OP_BILINEAR_ADD
     auto tracks = [&](int i) {
         const pp_op& op = net->ops[i];
-        if (op.type == PP_OP_UPSAMPLE_ADD) return true;
+        if (op.type == PP_OP_UPSAMPLE_ADD || op.type == PP_OP_BILINEAR_ADD) return true;
         return op.type == PP_OP_CONV && pp_conv_tracks_amax(net_conv_args(net, op, 1), is_h(i));
     };
     // pass 1: buffers a fp16-form convolution reads BEFORE any op of the program has written them = tensors from outside (the
@@ -379,7 +379,8 @@ static void net_plan_amax(pp_net* net) {
         {
             int covered = 0;
             const int out_b = net->ops[t.producers.front()].out;
-            for (int p : t.producers) covered += net->ops[p].type == PP_OP_CONV ? net->ops[p].cout : net->bufs[out_b].c;
+            for (int p : t.producers)      // the two slice writers: convolutions and PP_OP_BILINEAR_ADD (HRNetv2's resize + concatenate)
+                covered += net->ops[p].type == PP_OP_CONV || net->ops[p].type == PP_OP_BILINEAR_ADD ? net->ops[p].cout : net->bufs[out_b].c;
             if (covered < net->bufs[out_b].c) fused = false;
         }
         if (fused)
@@ -469,8 +470,8 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
     const int nb = (int)net.bufs.size();
     PP_REQUIRE(op.in >= 0 && op.in < nb && op.out >= 0 && op.out < nb, "op %d: buffer id out of range", idx);
     PP_REQUIRE(op.res1 < nb && op.res2 < nb, "op %d: residual buffer id out of range", idx);
-    PP_REQUIRE(op.in2 < nb && op.in3 < nb && (op.type == PP_OP_UPSAMPLE_ADD || (op.in2 < 0 && op.in3 < 0)),
-               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD only (-1 elsewhere)", idx);
+    PP_REQUIRE(op.in2 < nb && op.in3 < nb && (op.type == PP_OP_UPSAMPLE_ADD || op.type == PP_OP_BILINEAR_ADD || (op.in2 < 0 && op.in3 < 0)),
+               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD / PP_OP_BILINEAR_ADD only (-1 elsewhere)", idx);
     const pp_buf& bi = net.bufs[op.in];
     const pp_buf& bo = net.bufs[op.out];
     const int eh = op.pad_end & 1, ew = (op.pad_end >> 1) & 1;   // TensorFlow SAME: the odd padding row / column goes last
@@ -543,6 +544,23 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
             const int b = k ? op.in3 : op.in2, u = k ? op.up3_log2 : op.up2_log2;
             if (b >= 0)
                 PP_REQUIRE(u >= 0 && u <= 5 && net.bufs[b].c == bo.c && (net.bufs[b].h << u) == bo.h && (net.bufs[b].w << u) == bo.w &&
+                               b != op.out, "op %d: in%d must be [h >> up][w >> up][c] of the out buffer", idx, k + 2);
+        }
+    } else if (op.type == PP_OP_BILINEAR_ADD) {
+        PP_REQUIRE(op.cin == op.cout && op.cout > 0 && (op.cout & 3) == 0 && bi.c == op.cout && (bo.c & 3) == 0 &&
+                       op.out_c_off + op.cout <= bo.c && op.up_log2 >= 0 && op.up_log2 <= 5 && (bi.h << op.up_log2) == bo.h &&
+                       (bi.w << op.up_log2) == bo.w && op.in != op.out,
+                   "op %d: bilinear_add needs in [h][w][c] and out [h << up][w << up][>= out_c_off + c], c %% 4 == 0", idx);
+        PP_REQUIRE(op.relu == PP_RELU_NONE || op.relu == PP_RELU_LAST, "op %d: bilinear_add supports PP_RELU_NONE / PP_RELU_LAST", idx);
+        PP_REQUIRE(op.res2 < 0 && !op.out_nchw, "op %d: bilinear_add has no res2 and writes NHWC", idx);
+        if (op.res1 >= 0)
+            PP_REQUIRE(net.bufs[op.res1].c == op.cout && net.bufs[op.res1].h == bo.h && net.bufs[op.res1].w == bo.w && op.res1 != op.out,
+                       "op %d: res1 must be a [h << up][w << up][c] buffer other than out", idx);
+        PP_REQUIRE(op.in3 < 0 || op.in2 >= 0, "op %d: in3 without in2", idx);
+        for (int k = 0; k < 2; ++k) {
+            const int b = k ? op.in3 : op.in2, u = k ? op.up3_log2 : op.up2_log2;
+            if (b >= 0)
+                PP_REQUIRE(u >= 0 && u <= 5 && net.bufs[b].c == op.cout && (net.bufs[b].h << u) == bo.h && (net.bufs[b].w << u) == bo.w &&
                                b != op.out, "op %d: in%d must be [h >> up][w >> up][c] of the out buffer", idx, k + 2);
         }
     } else if (op.type == PP_OP_VIT_ENCODER) {
@@ -636,6 +654,12 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
                                       bo.c, op.up_log2, op.relu == PP_RELU_LAST, s, op.in2 >= 0 ? net->buf_ptr(op.in2) : nullptr,
                                       op.up2_log2, op.in3 >= 0 ? net->buf_ptr(op.in3) : nullptr, op.up3_log2,
                                       net->amax && net->op_y_slot[&op - net->ops.data()] >= 0 ? net->amax_slot(net->op_y_slot[&op - net->ops.data()]) : nullptr);
+    } else if (op.type == PP_OP_BILINEAR_ADD) {
+        const int slot = net->amax ? net->op_y_slot[&op - net->ops.data()] : -1;
+        return pp_launch_bilinear_add(net->buf_ptr(op.in), op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr, net->buf_ptr(op.out), batch,
+                                      bo.h, bo.w, op.cout, bo.c, op.out_c_off, op.up_log2, op.relu == PP_RELU_LAST, s,
+                                      op.in2 >= 0 ? net->buf_ptr(op.in2) : nullptr, op.up2_log2,
+                                      op.in3 >= 0 ? net->buf_ptr(op.in3) : nullptr, op.up3_log2, slot >= 0 ? net->amax_slot(slot) : nullptr);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         pp_vit_encoder* enc = net->vits[&op - net->ops.data()];
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);

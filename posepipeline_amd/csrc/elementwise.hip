@@ -72,6 +72,94 @@ __global__ __launch_bounds__(256) void upsample_add_kernel(const float4* __restr
     }
 }
 
+// PP_OP_BILINEAR_ADD: out[n][y][x][c_off + c] = act(((res1 + B(t)) + B(t2)) + B(t3)),  B = bilinear 2^u upsampling with half-pixel
+// centres (F.interpolate(mode='bilinear', align_corners=False)): the fuse layers of HRNetv2 (mmpose HRModule with
+// upsample_cfg mode='bilinear': 1x1 conv + BN on the coarser branch, bilinear upsample, `y += ...`) and the resize + concatenate in
+// front of its head (c_off selects the channel slice of the wider buffer).  For s = 2^u
+//   sy = max((y + 0.5) / s - 0.5, 0), y0 = floor(sy), y1 = min(y0 + 1, h - 1), ly1 = sy - y0, ly0 = 1 - ly1   (the same in x)
+//   B = ly0 * (lx0 * a00 + lx1 * a01) + ly1 * (lx0 * a10 + lx1 * a11)
+// The weights are dyadic fractions, exact in float32, and are computed from the output index (no table: two multiplies per
+// axis against four 16-byte loads per term); every product and every sum is rounded to float32 on its own (no FMA), so a CPU
+// restatement in the same order gives the same bits.  The four taps of neighbouring outputs overlap: the coarse maps (1/4 .. 1/64
+// of the fine map) are read through the caches, the fine map is written once.
+struct BilinTaps { int o00, o01, o10, o11; float ly0, ly1, lx0, lx1; };      // offsets in pixels of the coarse map
+__device__ __forceinline__ void bilin_axis(int i, int u, int n_src, int& i0, int& i1, float& l0, float& l1) {
+    const float inv = __uint_as_float((127u - (unsigned)u) << 23);                           // 2^-u
+    const float s = fmaxf(__fsub_rn(__fmul_rn(__fadd_rn((float)i, 0.5f), inv), 0.5f), 0.f);  // exact: dyadic
+    i0 = (int)s;
+    i1 = min(i0 + 1, n_src - 1);
+    l1 = __fsub_rn(s, (float)i0);
+    l0 = __fsub_rn(1.f, l1);
+}
+template <typename I>
+__device__ __forceinline__ float4 bilin_term(const float4* __restrict__ t, I n, int H, int W, int c4, int cc, int yy, int x, int u) {
+    const int hs = H >> u, ws = W >> u;
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    bilin_axis(yy, u, hs, y0, y1, ly0, ly1);
+    bilin_axis(x, u, ws, x0, x1, lx0, lx1);
+    const float4* base = t + (n * (I)hs * (I)ws) * (I)c4 + cc;
+    const float4 a00 = base[((I)y0 * ws + x0) * (I)c4], a01 = base[((I)y0 * ws + x1) * (I)c4];
+    const float4 a10 = base[((I)y1 * ws + x0) * (I)c4], a11 = base[((I)y1 * ws + x1) * (I)c4];
+    float4 v;
+#define PP_BILIN(f) v.f = __fadd_rn(__fmul_rn(ly0, __fadd_rn(__fmul_rn(lx0, a00.f), __fmul_rn(lx1, a01.f))), \
+                                    __fmul_rn(ly1, __fadd_rn(__fmul_rn(lx0, a10.f), __fmul_rn(lx1, a11.f))))
+    PP_BILIN(x); PP_BILIN(y); PP_BILIN(z); PP_BILIN(w);
+#undef PP_BILIN
+    return v;
+}
+__device__ __forceinline__ float4 add4_rn(const float4 a, const float4 b) {
+    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+}
+
+// same thread / block shape as upsample_add_kernel (UA_R float4 per thread, one atomic per block and sample for the maxima);
+// ys4 / yo4: float4 per pixel of the out buffer and the slice's offset in it.  I: the index type -- unsigned where every float4 index
+// of the launch fits 31 bits (every map of the networks here), so that the three divisions per element that take the index apart are
+// 32-bit ones; size_t beyond.
+template <typename I>
+__global__ __launch_bounds__(256) void bilinear_add_kernel(const float4* __restrict__ t, const float4* __restrict__ r1,
+                                                           float4* __restrict__ y, I total, int H, int W, int c4, int ys4,
+                                                           int yo4, int up, int relu, const float4* __restrict__ t2, int up2,
+                                                           const float4* __restrict__ t3, int up3, unsigned* y_amax) {
+    const I per = (I)H * (I)W * (I)c4;
+    const I b0 = (I)blockIdx.x * (I)(256 * UA_R);
+    const int img_first = (int)(b0 / per);
+    float ym[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < UA_R; ++r) {
+        const I i = b0 + (I)(r * 256) + threadIdx.x;
+        if (i >= total) break;
+        const int cc = (int)(i % (I)c4);
+        const I pix = i / (I)c4;                      // (n * H + yy) * W + x
+        I p = pix;
+        const int x = (int)(p % (I)W);
+        p /= (I)W;
+        const int yy = (int)(p % (I)H);
+        const I n = p / (I)H;
+        float4 v = bilin_term(t, n, H, W, c4, cc, yy, x, up);
+        if (r1) v = add4_rn(r1[i], v);
+        if (t2) v = add4_rn(v, bilin_term(t2, n, H, W, c4, cc, yy, x, up2));      // further terms, in mmpose's `y += ...` order
+        if (t3) v = add4_rn(v, bilin_term(t3, n, H, W, c4, cc, yy, x, up3));
+        if (relu) {
+            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        }
+        y[pix * (I)ys4 + yo4 + cc] = v;
+        if (y_amax) {
+            const float m = pp_abs4max(v);
+            const int d = (int)n - img_first;
+            if (d == 0) ym[0] = fmaxf(ym[0], m);
+            else if (d == 1) ym[1] = fmaxf(ym[1], m);
+            else if (m > 0.f) atomicMax(y_amax + n, __float_as_uint(m));
+        }
+    }
+    if (y_amax) {
+        __shared__ float red[16];
+        const I last = (b0 + (I)(256 * UA_R - 1) < total ? b0 + (I)(256 * UA_R - 1) : total - 1) / per;
+        const int im[2] = {img_first, img_first + 1};
+        pp_amax_commit_wg<4, 2>(y_amax, im, ym, img_first, (int)last > img_first ? img_first + 1 : img_first, red);
+    }
+}
+
 // PP_OP_AVGPOOL: nn.AvgPool2d((kh, kw), stride) without padding (the GlobalAveragePooling neck of mmtrack's ReID model,
 // mot/deepsort/deepsort_*.py:27): float32 sum over the window in (kh, kw) order, divided by the window size.
 __global__ __launch_bounds__(256) void avgpool_kernel(const float4* __restrict__ x, float4* __restrict__ y, size_t total, int Hin,
@@ -172,6 +260,32 @@ int pp_launch_upsample_add(const float* t, const float* res1, const float* res2,
                        reinterpret_cast<const float4*>(t), reinterpret_cast<const float4*>(res1),
                        reinterpret_cast<const float4*>(res2), reinterpret_cast<float4*>(y), total, H, W, c / 4, up_log2, relu,
                        reinterpret_cast<const float4*>(t2), up2, reinterpret_cast<const float4*>(t3), up3, y_amax);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+int pp_launch_bilinear_add(const float* t, const float* res1, float* y, int n, int H, int W, int c, int y_stride, int y_coff,
+                           int up_log2, int relu, hipStream_t stream, const float* t2, int up2, const float* t3, int up3,
+                           unsigned* y_amax) {
+    PP_REQUIRE(n > 0 && H > 0 && W > 0 && c > 0 && (c & 3) == 0 && (y_stride & 3) == 0 && (y_coff & 3) == 0 && y_coff >= 0 &&
+                   y_coff + c <= y_stride, "bilinear_add: channels [%d, %d) of %d must be multiples of 4 inside the out buffer", y_coff,
+               y_coff + c, y_stride);
+    const int ups[3] = {up_log2, t2 ? up2 : 0, t3 ? up3 : 0};
+    for (int u : ups)
+        PP_REQUIRE(u >= 0 && u <= 5 && (H >> u << u) == H && (W >> u << u) == W, "bilinear_add: %dx%d is not a multiple of 2^%d", H, W, u);
+    const size_t total = (size_t)n * H * W * (c / 4);
+    const dim3 grid((unsigned)((total + 256 * UA_R - 1) / (256 * UA_R)));
+    // the largest float4 index any thread forms: the out buffer's (the inputs and res1 are no larger), plus one block of slack for b0
+    if ((size_t)n * H * W * (y_stride / 4) + 256 * UA_R < ((size_t)1 << 31))
+        hipLaunchKernelGGL(bilinear_add_kernel<unsigned>, grid, dim3(256), 0, stream, reinterpret_cast<const float4*>(t),
+                           reinterpret_cast<const float4*>(res1), reinterpret_cast<float4*>(y), (unsigned)total, H, W, c / 4, y_stride / 4,
+                           y_coff / 4, up_log2, relu, reinterpret_cast<const float4*>(t2), up2, reinterpret_cast<const float4*>(t3), up3,
+                           y_amax);
+    else
+        hipLaunchKernelGGL(bilinear_add_kernel<size_t>, grid, dim3(256), 0, stream, reinterpret_cast<const float4*>(t),
+                           reinterpret_cast<const float4*>(res1), reinterpret_cast<float4*>(y), total, H, W, c / 4, y_stride / 4,
+                           y_coff / 4, up_log2, relu, reinterpret_cast<const float4*>(t2), up2, reinterpret_cast<const float4*>(t3), up3,
+                           y_amax);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -235,6 +235,11 @@ int pp_launch_depth_to_space(const float* x, float* y, int n, int h, int w, int 
 int pp_launch_upsample_add(const float* t, const float* res1, const float* res2, float* y, int n, int H, int W, int c,
                            int up_log2, int relu, hipStream_t stream, const float* t2 = nullptr, int up2 = 0,
                            const float* t3 = nullptr, int up3 = 0, unsigned* y_amax = nullptr);   // y_amax: pp_amax.h
+// y[n][H][W][y_coff + c of y_stride] = act(((res1 + B(t)) + B(t2)) + B(t3)), B = bilinear 2^u upsampling, half-pixel centres
+// (elementwise.hip; res1 / t2 / t3 may be null)
+int pp_launch_bilinear_add(const float* t, const float* res1, float* y, int n, int H, int W, int c, int y_stride, int y_coff,
+                           int up_log2, int relu, hipStream_t stream, const float* t2 = nullptr, int up2 = 0,
+                           const float* t3 = nullptr, int up3 = 0, unsigned* y_amax = nullptr);
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

@@ -152,6 +152,17 @@ class _Relation:
     def proj(self):
         return self
 
+    def __getattr__(self, name):
+        """a method the table class defines, called on a restricted view as DataJoint allows --
+        `(HandPoseEstimationMethodLookup & key).joint_names()`: the view is its `self`"""
+        import inspect
+        import types
+        table = self.__dict__.get("table")
+        f = table.__dict__.get(name) if table is not None else None
+        if inspect.isfunction(f):
+            return types.MethodType(f, self)
+        raise AttributeError(name)
+
 
 def _as_relation(x):
     if isinstance(x, _Relation):

@@ -86,7 +86,8 @@ def _conv_bn(shapes, conv, bn, cout, cin, k):
         shapes[bn + "." + s] = (cout,)
 
 
-def hrnet_param_shapes(spec: HRNetSpec) -> dict:
+def hrnet_backbone_shapes(spec, multiscale_output=False) -> dict:
+    """the `backbone.*` parameters; multiscale_output: the last module keeps all its fuse layers (HRNetv2, models/hrnetv2.py)"""
     sh: dict = {}
     B = "backbone."
     _conv_bn(sh, B + "conv1", B + "bn1", 64, 3, 3)
@@ -122,7 +123,7 @@ def hrnet_param_shapes(spec: HRNetSpec) -> dict:
                     _conv_bn(sh, p + "conv1", p + "bn1", cur[b], cur[b], 3)
                     _conv_bn(sh, p + "conv2", p + "bn2", cur[b], cur[b], 3)
             last = (si == len(spec.stages) - 1) and (m == n_mod - 1)
-            n_out = 1 if last else n_br
+            n_out = 1 if last and not multiscale_output else n_br
             for i in range(n_out):
                 for j in range(n_br):
                     f = f"{mp}fuse_layers.{i}.{j}."
@@ -133,6 +134,12 @@ def hrnet_param_shapes(spec: HRNetSpec) -> dict:
                             cout = cur[i] if k == i - j - 1 else cur[j]
                             _conv_bn(sh, f"{f}{k}.0", f"{f}{k}.1", cout, cur[j], 3)
         pre = cur
+    return sh
+
+
+def hrnet_param_shapes(spec: HRNetSpec) -> dict:
+    sh = hrnet_backbone_shapes(spec)
+    ch = spec.channels
     sh["keypoint_head.final_layer.weight"] = (spec.num_joints, ch[0], 1, 1)
     sh["keypoint_head.final_layer.bias"] = (spec.num_joints,)
     return sh
@@ -140,6 +147,9 @@ def hrnet_param_shapes(spec: HRNetSpec) -> dict:
 
 # ---- program builder -----------------------------------------------------------------------------
 class _HR:
+    multiscale_output = False      # the last module has every fuse output (HRNetv2)
+    bilinear_fuse = False          # the coarse-to-fine fuse terms are upsampled bilinearly: one PP_OP_BILINEAR_ADD pass, no "conv" form
+
     def __init__(self, spec, sd):
         self.spec, self.sd, self.pb = spec, sd, ProgramBuilder()
 
@@ -176,7 +186,7 @@ class _HR:
             acc = -1
             j = 0
             ups = []                                    # "onepass": the coarse terms (buffer, up_log2), j > i, added at the end
-            onepass = FUSE_MODE == "onepass"
+            onepass = FUSE_MODE == "onepass" or self.bilinear_fuse
             while j < n_br:
                 if j == i:
                     assert acc == -1 and i == 0
@@ -205,12 +215,16 @@ class _HR:
                 j += 2 if absorb else 1
             if ups:
                 # y = relu(((acc + up(t_a)) + up(t_b)) + up(t_c)): every coarse term of this output in one pass
-                acc = pb.upsample_add(ups[0][0], up_log2=ups[0][1], res1=acc, relu=L.PP_RELU_LAST, more=ups[1:],
-                                      name=f"{mp}fuse_layers.{i}.up")
+                acc = self.fuse_up(ups, acc, f"{mp}fuse_layers.{i}.up")
             outs.append(acc)
         return outs
 
-    def build(self) -> Program:
+    def fuse_up(self, ups, acc, name):
+        """the coarse-to-fine terms [(buffer, up_log2), ...] of one fuse output, added to the partial sum `acc`, then ReLU"""
+        return self.pb.upsample_add(ups[0][0], up_log2=ups[0][1], res1=acc, relu=L.PP_RELU_LAST, more=ups[1:], name=name)
+
+    def backbone(self):
+        """stem .. stage4 -> the last module's outputs (one buffer, or one per branch with multiscale_output)"""
         spec, pb = self.spec, self.pb
         R = L.PP_RELU_LAST
         B = "backbone."
@@ -239,9 +253,14 @@ class _HR:
                     xs.append(y)
             for m in range(n_mod):
                 last = (si == len(spec.stages) - 1) and (m == n_mod - 1)
-                xs = self.module(xs, f"{B}stage{si + 2}.{m}.", 1 if last else n_br)
+                xs = self.module(xs, f"{B}stage{si + 2}.{m}.", 1 if last and not self.multiscale_output else n_br)
             ys = xs
             pre = cur
+        return ys
+
+    def build(self) -> Program:
+        spec, pb = self.spec, self.pb
+        ys = self.backbone()
         hh, hw = spec.heatmap_hw
         out = pb.buf(hh, hw, spec.num_joints, name="output")
         sd = self.sd

@@ -350,3 +350,118 @@ class LiftingPerson(dj.Computed):  # pipeline.py:1252-1257
         return ["Hip (root)", "Right hip", "Right knee", "Right foot", "Left hip", "Left knee", "Left foot", "Spine",
                 "Thorax", "Nose", "Head", "Left shoulder", "Left elbow", "Left wrist", "Right shoulder", "Right elbow",
                 "Right wrist"]
+
+
+# ---- hand stage (pipeline.py:1979-2146) --------------------------------------------------------------------------------
+@schema
+class HandBboxMethodLookup(dj.Lookup):  # pipeline.py:1980-1990
+    definition = """
+    detection_method      : int
+    ---
+    detection_method_name : varchar(50)
+    """
+    contents = [
+        {"detection_method": 0, "detection_method_name": "RTMDet"},
+        {"detection_method": 1, "detection_method_name": "TopDown"},
+    ]
+
+
+@schema
+class HandBboxMethod(dj.Manual):  # pipeline.py:1993-1998
+    definition = """
+    -> Video
+    -> HandBboxMethodLookup
+    ---
+    """
+
+
+@schema
+class HandBbox(dj.Computed):  # pipeline.py:2002-2008
+    definition = """
+    -> HandBboxMethod
+    ---
+    num_boxes   :   int
+    bboxes      :   longblob
+    """
+
+    def make(self, key):  # pipeline.py:2009-2029
+        name = (HandBboxMethodLookup & key).fetch1("detection_method_name")
+        if name == "RTMDet":
+            from .wrappers.hand_bbox import mmpose_hand_det
+            num_boxes, bboxes = mmpose_hand_det(key=key, method="RTMDet")      # not built: raises NotImplementedError
+            key["bboxes"] = bboxes
+            key["num_boxes"] = num_boxes
+        elif name == "TopDown":
+            # right / left hand boxes from the Halpe keypoints of the TopDownPerson table
+            from .wrappers.hand_bbox import make_bbox_from_keypoints
+            try:
+                keypoints = (TopDownPerson & key & "top_down_method=2").fetch1("keypoints")
+            except Exception:
+                raise Exception("TopDownPerson table does not have the required keypoints")
+            key["bboxes"] = make_bbox_from_keypoints(keypoints)
+            key["num_boxes"] = 2
+        else:
+            raise Exception("Method not implemented")
+        self.insert1(key)
+
+
+_HAND_JOINTS = ["Wrist", "CMC1", "MCP1", "IP1", "TIP1", "MCP2", "PIP2", "DIP2", "TIP2", "MCP3", "PIP3", "DIP3", "TIP3", "MCP4",
+                "PIP4", "DIP4", "TIP4", "MCP5", "PIP5", "DIP5", "TIP5"]
+_HAND_JOINTS_RHD = ["Wrist", "TIP1", "IP1", "MCP1", "CMC1", "TIP2", "DIP2", "PIP2", "MCP2", "TIP3", "DIP3", "PIP3", "MCP3", "TIP4",
+                    "DIP4", "PIP4", "MCP4", "TIP5", "DIP5", "PIP5", "MCP5"]
+
+
+@schema
+class HandPoseEstimationMethodLookup(dj.Lookup):  # pipeline.py:2032-2045
+    definition = """
+    estimation_method      : int
+    ---
+    estimation_method_name : varchar(50)
+    """
+    contents = [
+        {"estimation_method": -1, "estimation_method_name": "Halpe"},
+        {"estimation_method": 0, "estimation_method_name": "RTMPoseHand5"},
+        {"estimation_method": 1, "estimation_method_name": "RTMPoseCOCO"},
+        {"estimation_method": 2, "estimation_method_name": "freihand"},
+        {"estimation_method": 3, "estimation_method_name": "HRNet_dark"},
+        {"estimation_method": 4, "estimation_method_name": "HRNet_udp"},
+    ]
+
+    def joint_names(self):
+        """pipeline.py:2047-2103, called on a restricted view: `(HandPoseEstimationMethodLookup & key).joint_names()`.  42 names
+        (right, then left) for every method but HRNet_dark, whose 21 names are the rhd2d joint order (the reference's quirk)."""
+        method = self.fetch1("estimation_method_name")
+        if method in ("RTMPoseHand5", "RTMPoseCOCO", "freihand", "HRNet_udp", "Halpe"):
+            return [n.lower() + "_r" for n in _HAND_JOINTS] + [n.lower() + "_l" for n in _HAND_JOINTS]
+        elif method == "HRNet_dark":
+            return list(_HAND_JOINTS_RHD)
+
+
+@schema
+class HandPoseEstimationMethod(dj.Manual):  # pipeline.py:2107-2112
+    definition = """
+    -> HandBbox
+    -> HandPoseEstimationMethodLookup
+    ---
+    """
+
+
+@schema
+class HandPoseEstimation(dj.Computed):  # pipeline.py:2116-2121
+    definition = """
+    -> HandPoseEstimationMethod
+    ---
+    keypoints_2d       : longblob  #(time, [21 righthand-21 lefthand], 3)
+    """
+
+    def make(self, key):  # pipeline.py:2122-2146
+        name = (HandPoseEstimationMethodLookup & key).fetch1("estimation_method_name")
+        if name in ("HRNet_dark", "HRNet_udp"):
+            from .wrappers.hand_estimation import mmpose_HPE
+            key["keypoints_2d"] = mmpose_HPE(key, name)
+        elif name == "Halpe":      # the hands of the Halpe-136 body model themselves: right 21, then left 21
+            kp2d = (TopDownPerson & key & "top_down_method=2").fetch1("keypoints")
+            key["keypoints_2d"] = np.concatenate((kp2d[:, -21:, :], kp2d[:, -42:-21, :]), axis=1)
+        else:                      # RTMPoseHand5 / RTMPoseCOCO / freihand: other model families, not built
+            raise Exception("Method not implemented")
+        self.insert1(key)

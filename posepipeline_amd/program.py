@@ -201,6 +201,35 @@ class ProgramBuilder:
                               in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, flops=0.0))
         return out
 
+    def bilinear_add(self, t, *, up_log2, res1=-1, relu=L.PP_RELU_NONE, more=(), out=None, out_c_off=0,
+                     name="bilinear_add") -> int:
+        """out[..., out_c_off : out_c_off + c] = act(((res1 + B(t, 2^up_log2)) + B(t2, 2^u2)) + B(t3, 2^u3)), B = bilinear upsampling
+        with half-pixel centres (F.interpolate(mode='bilinear', align_corners=False)): the accumulate step(s) of an HRNetv2 fuse
+        layer in one pass (PP_OP_BILINEAR_ADD).  more: up to two further coarse terms [(buffer, up_log2), ...], added in this
+        order.  out / out_c_off: write a channel slice of an existing wider buffer (resize + concatenate)."""
+        h, w, c = self.dims(t)
+        assert c % 4 == 0 and 0 <= up_log2 <= 5, (c, up_log2)
+        ho, wo = h << up_log2, w << up_log2
+        if out is None:
+            assert out_c_off == 0
+            out = self.buf(ho, wo, c)
+        else:
+            oh, ow, oc = self.dims(out)
+            assert (oh, ow) == (ho, wo) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + c <= oc, (self.dims(out), ho, wo, c, out_c_off)
+        if res1 >= 0:
+            assert self.dims(res1) == (ho, wo, c), (self.dims(res1), ho, wo, c)
+        more = list(more)
+        assert len(more) <= 2
+        for tb, ub in more:
+            assert 0 <= ub <= 5 and self.dims(tb) == (ho >> ub, wo >> ub, c) and (ho >> ub << ub, wo >> ub << ub) == (ho, wo), \
+                (self.dims(tb), ho, wo, ub)
+        (in2, up2), (in3, up3) = (more + [(-1, 0), (-1, 0)])[:2]
+        self.vops.append(dict(type=L.PP_OP_BILINEAR_ADD, in_=t, out=out, res1=res1, res2=-1, cin=c, cout=c, kh=1, kw=1,
+                              stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=relu, up_log2=up_log2, out_nchw=0,
+                              res1_shift=0, res1_off_w=0, out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name,
+                              in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, flops=0.0))
+        return out
+
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
         a 4-term gather (PP_OP_DECONV_BF16).  weight: torch ConvTranspose2d layout [cin][cout][4][4], BN already folded."""
