@@ -47,7 +47,9 @@ extern "C" {
                                  pp_detector_constants
                               10: pp_detector_enable_margins / pp_detector_margins (per-frame decision margins of the detection path);
                                  pp_net_input_amax is a one-shot promise; PP_OP_BILINEAR_ADD (an added op type over existing pp_op
-                                 fields: no struct or signature changed, so the version stays 10) */
+                                 fields: no struct or signature changed, so the version stays 10);
+                                 PP_OP_DWCONV3X3 / PP_OP_LAYERNORM / PP_OP_WINDOW_ATTN / PP_OP_GELU_ADD and PP_ACT_GELU (the HRFormer
+                                 blocks) were added the same way */
 
 typedef enum {
     PP_OK = 0,
@@ -150,6 +152,37 @@ typedef enum {
                                 PP_RELU_NONE / PP_RELU_LAST) and, with out_c_off, the resize + concatenate in front of its head: channels
                                 [out_c_off, out_c_off + cout) of a wider NHWC `out`, the others untouched.  cin == cout, % 4 == 0.
                                 Uses existing pp_op fields only: sizeof(pp_op) and PP_ABI_VERSION are unchanged */
+    /* The ops of an HRFormer block (mmpose 0.x backbones/hrformer.py; models/hrformer.py), float32 on the vector ALU (hrformer.hip).
+     * They use existing pp_op fields only -- sizeof(pp_op) and PP_ABI_VERSION are unchanged -- and every field not named below keeps
+     * its neutral value (res1 / res2 / in2 / in3 = -1, offsets 0).  erf and exp are evaluated in double and rounded once. */
+    PP_OP_DWCONV3X3 = 11,    /* depthwise 3x3 convolution, padding 1: in [h][w][c] -> out [(h - 1) / s + 1][(w - 1) / s + 1][c];
+                                cin = cout = c (the buffers' channels, % 4 == 0), kh = kw = 3, stride = s in {1, 2}, pad_h = pad_w = 1;
+                                w_off: w[9][c] (tap ky * 3 + kx major, BN folded), b_off: bias[c].
+                                out = act(bias + sum over (ky, kx) in that order of g(in) * w): acc = bias, then acc = acc + x * w with the
+                                product and the sum each rounded to float32 (no FMA); taps outside the map are skipped.
+                                relu: the output's activation, PP_RELU_NONE / PP_RELU_LAST / PP_ACT_GELU;
+                                pad_end bit 0 (PP_DW_GELU_IN): g = GELU applied to every input value read (stride 1 only; CrossFFN's
+                                fc1 activation lives here, not in the convolution kernels), else g = identity */
+    PP_OP_LAYERNORM = 12,    /* LayerNorm over the channels of every pixel: in, out [h][w][cout] (distinct buffers); cin = c_real <= cout =
+                                the buffers' channels (% 4 == 0, <= 1024); w_off: gamma[cout], b_off: beta[cout] followed by eps (one
+                                float).  mean and the biased variance run over the first c_real channels (two passes: sum, then sum of
+                                squared deviations), out = (x - mean) / sqrt(var + eps) * gamma + beta; channels >= c_real are written as
+                                exact zeros whatever `in` holds there */
+    PP_OP_WINDOW_ATTN = 13,  /* 7x7 local-window multi-head self-attention with a relative-position bias (LocalWindowSelfAttention +
+                                WindowMSA, with_rpe, no pad mask).  in [h][w][3 * cout] = the qkv map, a 1x1 PP_OP_CONV of the LayerNorm
+                                output: channel s * cout + head * hd + d holds (q, k, v)[s] of head `head`, s = 0, 1, 2, hd = cin / heads;
+                                channels [cin, cout) of each third are padding.  out [h][w][cout].  cin = c_real = heads * hd (hd <= 64),
+                                cout = the out buffer's channels (% 4 == 0), kh = kw = 7, stride = heads;
+                                w_off: table[169][heads] (relative_position_bias_table), b_off: the qkv bias in the layout of `in`
+                                ([3 * cout]; the k and v thirds are read).
+                                The map is zero-padded to multiples of 7 with pad / 2 rows (columns) in front and the rest behind, and cut
+                                into 7x7 windows.  Per window and head, over its 49 tokens i, j = (y, x) row-major:
+                                  attn[i][j] = (q_i * hd^-0.5) . k_j + table[(y_i - y_j + 6) * 13 + (x_i - x_j + 6)][head],
+                                  out_i = sum_j softmax_j(attn[i][j]) v_j.
+                                A padded token takes part as a key with k = b_k, v = b_v (mmpose pads BEFORE the qkv Linear, and
+                                0 . W + b = b exactly); its own output is cropped away.  Channels [cin, cout) of `out` are exact zeros */
+    PP_OP_GELU_ADD = 14      /* out = res1 + gelu(in) (res1 = -1: out = gelu(in)); in, res1, out [h][w][c], cin = cout = c % 4 == 0, out
+                                distinct from in and res1.  The last GELU of CrossFFN and the block's residual add in one pass */
 } pp_op_type;
 
 #define PP_RELU_NONE 0
@@ -162,6 +195,9 @@ typedef enum {
 #define PP_ACT_MISH 4    /* x * tanh(softplus(x)) */
 #define PP_ACT_ELU 5     /* x > 0 ? x : exp(x) - 1 */
 #define PP_ACT_SWISH 6   /* x * sigmoid(x)  (mmcv Swish: YOLOX of the ByteTrack config, _base_/models/yolox_x_8x8.py) */
+/* PP_OP_DWCONV3X3 only (the convolution kernels have no GELU): 0.5 x (1 + erf(x / sqrt 2)) in double, rounded once */
+#define PP_ACT_GELU 7
+#define PP_DW_GELU_IN 1  /* pp_op.pad_end of a PP_OP_DWCONV3X3: GELU on the input values */
 
 typedef struct pp_op {
     int32_t type;

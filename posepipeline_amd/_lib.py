@@ -19,8 +19,11 @@ PP_OP_CONV, PP_OP_MAXPOOL, PP_OP_ROIALIGN, PP_OP_COPY, PP_OP_VIT_ENCODER, PP_OP_
 PP_OP_DECONV_BF16 = 8
 PP_OP_AVGPOOL = 9
 PP_OP_BILINEAR_ADD = 10
+PP_OP_DWCONV3X3, PP_OP_LAYERNORM, PP_OP_WINDOW_ATTN, PP_OP_GELU_ADD = 11, 12, 13, 14     # the HRFormer block ops (hrformer.hip)
 PP_RELU_NONE, PP_RELU_LAST, PP_RELU_FIRST = 0, 1, 2
 PP_ACT_LEAKY, PP_ACT_MISH, PP_ACT_ELU, PP_ACT_SWISH = 3, 4, 5, 6
+PP_ACT_GELU = 7          # PP_OP_DWCONV3X3 only
+PP_DW_GELU_IN = 1        # pp_op.pad_end of a PP_OP_DWCONV3X3
 PP_NET_NUMERICS_DEFAULT, PP_NET_NUMERICS_EXACT, PP_NET_NUMERICS_SPLIT = 0, 1, 2
 PP_NET_NUMERICS_SPLIT_BF16, PP_NET_NUMERICS_SPLIT_F16 = 3, 4
 # "split": the form pp_conv_split_kind / POSEPIPE_SPLIT_F16 select when the net is created; the two forms by name

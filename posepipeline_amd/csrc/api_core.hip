@@ -563,6 +563,43 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
                 PP_REQUIRE(u >= 0 && u <= 5 && net.bufs[b].c == op.cout && (net.bufs[b].h << u) == bo.h && (net.bufs[b].w << u) == bo.w &&
                                b != op.out, "op %d: in%d must be [h >> up][w >> up][c] of the out buffer", idx, k + 2);
         }
+    } else if (op.type == PP_OP_DWCONV3X3) {
+        PP_REQUIRE(op.cin == op.cout && op.cout > 0 && (op.cout & 3) == 0 && bi.c == op.cout && bo.c == op.cout && op.in != op.out,
+                   "op %d: dwconv3x3 needs distinct in / out buffers of cin == cout channels, a multiple of 4", idx);
+        PP_REQUIRE(op.kh == 3 && op.kw == 3 && op.pad_h == 1 && op.pad_w == 1 && (op.stride == 1 || op.stride == 2) &&
+                       bo.h == (bi.h - 1) / op.stride + 1 && bo.w == (bi.w - 1) / op.stride + 1,
+                   "op %d: dwconv3x3 is 3x3, padding 1, stride 1 or 2: in [h][w][c] -> out [(h - 1) / s + 1][(w - 1) / s + 1][c]", idx);
+        PP_REQUIRE(op.relu == PP_RELU_NONE || op.relu == PP_RELU_LAST || op.relu == PP_ACT_GELU,
+                   "op %d: dwconv3x3 supports PP_RELU_NONE / PP_RELU_LAST / PP_ACT_GELU", idx);
+        PP_REQUIRE((op.pad_end & ~PP_DW_GELU_IN) == 0 && (!(op.pad_end & PP_DW_GELU_IN) || op.stride == 1),
+                   "op %d: dwconv3x3 pad_end is 0 or PP_DW_GELU_IN (stride 1 only)", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0 && op.up_log2 == 0, "op %d: dwconv3x3 has no residuals, slices or upsampling", idx);
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)9 * op.cout <= net.n_weights && op.b_off >= 0 &&
+                       (op.b_off % 4) == 0 && (size_t)op.b_off + op.cout <= net.n_weights, "op %d: dwconv3x3 parameters out of blob", idx);
+    } else if (op.type == PP_OP_LAYERNORM) {
+        PP_REQUIRE(op.cin > 0 && op.cin <= op.cout && (op.cout & 3) == 0 && op.cout <= 1024 && bi.c == op.cout && bo.c == op.cout &&
+                       bi.h == bo.h && bi.w == bo.w && op.in != op.out,
+                   "op %d: layernorm needs distinct in / out buffers [h][w][cout], cin <= cout real channels, cout %% 4 == 0, <= 1024", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0, "op %d: layernorm has no residuals or slices", idx);
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + op.cout <= net.n_weights && op.b_off >= 0 &&
+                       (op.b_off % 4) == 0 && (size_t)op.b_off + op.cout + 1 <= net.n_weights, "op %d: layernorm parameters out of blob", idx);
+    } else if (op.type == PP_OP_WINDOW_ATTN) {
+        PP_REQUIRE(op.stride > 0 && op.cin > 0 && op.cin % op.stride == 0 && op.cin <= op.cout && (op.cout & 3) == 0 &&
+                       op.cin / op.stride <= pp_window_attn_max_head_dim(),
+                   "op %d: window_attn needs cin = heads (stride) * head dim (at most %d) <= cout, cout %% 4 == 0", idx, pp_window_attn_max_head_dim());
+        PP_REQUIRE(bi.c == 3 * op.cout && bo.c == op.cout && bi.h == bo.h && bi.w == bo.w && op.in != op.out,
+                   "op %d: window_attn needs in [h][w][3 * cout] (the qkv map) and out [h][w][cout]", idx);
+        PP_REQUIRE(op.kh == 7 && op.kw == 7, "op %d: window_attn supports 7x7 windows", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0, "op %d: window_attn has no residuals or slices", idx);
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)169 * op.stride <= net.n_weights && op.b_off >= 0 &&
+                       (op.b_off % 4) == 0 && (size_t)op.b_off + (size_t)3 * op.cout <= net.n_weights, "op %d: window_attn parameters out of blob", idx);
+    } else if (op.type == PP_OP_GELU_ADD) {
+        PP_REQUIRE(op.cin == op.cout && op.cout > 0 && (op.cout & 3) == 0 && bi.c == op.cout && bo.c == op.cout && bi.h == bo.h &&
+                       bi.w == bo.w && op.in != op.out, "op %d: gelu_add needs distinct in / out buffers [h][w][c], c %% 4 == 0", idx);
+        PP_REQUIRE(op.res2 < 0 && !op.out_nchw && op.out_c_off == 0, "op %d: gelu_add has no res2 or slices", idx);
+        if (op.res1 >= 0)
+            PP_REQUIRE(net.bufs[op.res1].c == bo.c && net.bufs[op.res1].h == bo.h && net.bufs[op.res1].w == bo.w && op.res1 != op.out,
+                       "op %d: gelu_add res1 must be a [h][w][c] buffer other than out", idx);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         PP_REQUIRE(op.cin == op.cout && bi.c == op.cin && bo.c == op.cin && bi.h == bo.h && bi.w == bo.w && op.in != op.out,
                    "op %d: vit encoder needs distinct in / out buffers of [h][w][dim]", idx);
@@ -660,6 +697,18 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
                                       bo.h, bo.w, op.cout, bo.c, op.out_c_off, op.up_log2, op.relu == PP_RELU_LAST, s,
                                       op.in2 >= 0 ? net->buf_ptr(op.in2) : nullptr, op.up2_log2,
                                       op.in3 >= 0 ? net->buf_ptr(op.in3) : nullptr, op.up3_log2, slot >= 0 ? net->amax_slot(slot) : nullptr);
+    } else if (op.type == PP_OP_DWCONV3X3) {
+        return pp_launch_dwconv3x3(net->buf_ptr(op.in), net->weights + op.w_off, net->weights + op.b_off, net->buf_ptr(op.out), batch,
+                                   bi.h, bi.w, op.cout, op.stride, op.relu, op.pad_end & PP_DW_GELU_IN, s);
+    } else if (op.type == PP_OP_LAYERNORM) {
+        return pp_launch_layernorm_nhwc(net->buf_ptr(op.in), net->weights + op.w_off, net->weights + op.b_off,
+                                        net->buf_ptr(op.out), (size_t)batch * bi.h * bi.w, op.cin, op.cout, s);
+    } else if (op.type == PP_OP_WINDOW_ATTN) {
+        return pp_launch_window_attn(net->buf_ptr(op.in), net->weights + op.w_off, net->weights + op.b_off, net->buf_ptr(op.out), batch,
+                                     bi.h, bi.w, op.cin, op.cout, op.stride, s);
+    } else if (op.type == PP_OP_GELU_ADD) {
+        return pp_launch_gelu_add(net->buf_ptr(op.in), op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr, net->buf_ptr(op.out),
+                                  (size_t)batch * net->buf_elems[op.in], s);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         pp_vit_encoder* enc = net->vits[&op - net->ops.data()];
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);

@@ -240,6 +240,19 @@ int pp_launch_upsample_add(const float* t, const float* res1, const float* res2,
 int pp_launch_bilinear_add(const float* t, const float* res1, float* y, int n, int H, int W, int c, int y_stride, int y_coff,
                            int up_log2, int relu, hipStream_t stream, const float* t2 = nullptr, int up2 = 0,
                            const float* t3 = nullptr, int up3 = 0, unsigned* y_amax = nullptr);
+// ---- HRFormer block ops (hrformer.hip; field by field in posepipe_hip.h) ------------------------------------------------------
+// depthwise 3x3, padding 1, NHWC, c % 4 == 0; w [9][c], bias [c]; act: PP_RELU_NONE / PP_RELU_LAST / PP_ACT_GELU; gelu_in: stride 1 only
+int pp_launch_dwconv3x3(const float* x, const float* w, const float* bias, float* y, int n, int hin, int win, int c, int stride,
+                        int act, int gelu_in, hipStream_t stream);
+// LayerNorm over the first c_real of c_buf channels of `rows` pixels; channels >= c_real are written as zeros; beta_eps: beta[c_buf], eps
+int pp_launch_layernorm_nhwc(const float* x, const float* gamma, const float* beta_eps, float* y, size_t rows, int c_real,
+                             int c_buf, hipStream_t stream);
+// y = res + gelu(x) (res may be null), elems % 4 == 0
+int pp_launch_gelu_add(const float* x, const float* res, float* y, size_t elems, hipStream_t stream);
+// 7x7 window attention: qkv [n][h][w][3 * c_buf] -> out [n][h][w][c_buf]; table [169][heads], bias [3 * c_buf]
+int pp_launch_window_attn(const float* qkv, const float* table, const float* bias, float* out, int n, int h, int w, int c_real,
+                          int c_buf, int heads, hipStream_t stream);
+int pp_window_attn_max_head_dim();
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

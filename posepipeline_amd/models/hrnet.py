@@ -148,6 +148,7 @@ def hrnet_param_shapes(spec: HRNetSpec) -> dict:
 # ---- program builder -----------------------------------------------------------------------------
 class _HR:
     multiscale_output = False      # the last module has every fuse output (HRNetv2)
+    layer1_blocks = 4              # Bottlenecks of layer1 (HRFormer: 2)
     bilinear_fuse = False          # the coarse-to-fine fuse terms are upsampled bilinearly: one PP_OP_BILINEAR_ADD pass, no "conv" form
 
     def __init__(self, spec, sd):
@@ -177,7 +178,7 @@ class _HR:
         xs = list(xs)
         for b in range(n_br):
             for k in range(spec.blocks_per_branch):
-                xs[b] = self.basic(xs[b], f"{mp}branches.{b}.{k}.")
+                xs[b] = self.branch_block(xs[b], f"{mp}branches.{b}.{k}.", b)
         outs = []
         for i in range(n_out):
             # terms T_j in mmpose's order j = 0..n_br-1:  y = ((T_0 + T_1) + T_2) + ...; relu(y).
@@ -206,18 +207,25 @@ class _HR:
                         acc = self.cb(xs[j], f + "0", f + "1", pad=0, relu=relu, res1=acc, up_log2=j - i,
                                       out=pb.buf(h, w, c))
                 else:
-                    y = xs[j]
-                    for k in range(i - j - 1):
-                        y = self.cb(y, f"{f}{k}.0", f"{f}{k}.1", stride=2, relu=L.PP_RELU_LAST)
-                    k = i - j - 1
-                    acc = self.cb(y, f"{f}{k}.0", f"{f}{k}.1", stride=2, relu=relu, res1=acc,
-                                  res2=xs[i] if absorb else -1)
+                    acc = self.fuse_down(xs[j], f, i - j, relu, acc, xs[i] if absorb else -1)
                 j += 2 if absorb else 1
             if ups:
                 # y = relu(((acc + up(t_a)) + up(t_b)) + up(t_c)): every coarse term of this output in one pass
                 acc = self.fuse_up(ups, acc, f"{mp}fuse_layers.{i}.up")
             outs.append(acc)
         return outs
+
+    def branch_block(self, x, p, branch):
+        """one block of branch `branch` (HRNet: a BasicBlock)"""
+        return self.basic(x, p)
+
+    def fuse_down(self, y, f, steps, relu, acc, res2):
+        """the fine-to-coarse term of a fuse layer: `steps` strided 3x3 conv + BN (ReLU after all but the last); the last
+        one's epilogue adds the partial sum `acc` (and the identity term `res2` when it directly follows) and applies `relu`"""
+        for k in range(steps - 1):
+            y = self.cb(y, f"{f}{k}.0", f"{f}{k}.1", stride=2, relu=L.PP_RELU_LAST)
+        k = steps - 1
+        return self.cb(y, f"{f}{k}.0", f"{f}{k}.1", stride=2, relu=relu, res1=acc, res2=res2)
 
     def fuse_up(self, ups, acc, name):
         """the coarse-to-fine terms [(buffer, up_log2), ...] of one fuse output, added to the partial sum `acc`, then ReLU"""
@@ -231,7 +239,7 @@ class _HR:
         x = pb.buf(spec.in_h, spec.in_w, 4, name="input")     # RGB + one zero channel (Cin % 4 == 0)
         x = self.cb(x, B + "conv1", B + "bn1", stride=2, relu=R)
         x = self.cb(x, B + "conv2", B + "bn2", stride=2, relu=R)
-        for i in range(4):
+        for i in range(self.layer1_blocks):
             x = self.bottleneck(x, f"{B}layer1.{i}.", i == 0)
         ch = spec.channels
         ys = [x]

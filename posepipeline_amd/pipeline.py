@@ -287,6 +287,8 @@ class TopDownPerson(dj.Computed):  # pipeline.py:1011-1015
             key["keypoints"] = mmpose_top_down_person(key, "HRNet_W48_COCOWholeBody")
         elif method_name == "MMPoseHalpe":
             key["keypoints"] = mmpose_top_down_person(key, "HRNet_W48_HALPE")
+        elif method_name == "MMPoseHrformerCoco":
+            key["keypoints"] = mmpose_top_down_person(key, "HRFormer_COCO")
         elif method_name in ("ViTPoseB", "ViTPoseL", "ViTPoseH"):      # extension, see TopDownMethodLookup
             key["keypoints"] = mmpose_top_down_person(key, "ViTPose_%s_COCO" % method_name[-1])
         else:

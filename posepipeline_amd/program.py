@@ -230,6 +230,83 @@ class ProgramBuilder:
                               in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, flops=0.0))
         return out
 
+    # ---- HRFormer block ops (PP_OP_DWCONV3X3 / _LAYERNORM / _WINDOW_ATTN / _GELU_ADD; include/posepipe_hip.h) -------------------
+    def dwconv3x3(self, x, weight, bias, *, stride=1, act=L.PP_RELU_NONE, gelu_in=False, name="dwconv3x3") -> int:
+        """Depthwise 3x3 convolution, padding 1.  weight: torch layout [c][1][3][3] (BN already folded), bias [c] or None; both are
+        zero-padded to the buffer's channels.  act: PP_RELU_NONE / PP_RELU_LAST / PP_ACT_GELU on the output; gelu_in: GELU on every
+        input value (stride 1 only)."""
+        h, w, c_buf = self.dims(x)
+        wt = np.asarray(weight, dtype=np.float32)
+        c = wt.shape[0]
+        assert wt.shape == (c, 1, 3, 3) and c <= c_buf and c_buf % 4 == 0 and stride in (1, 2), (wt.shape, c_buf, stride)
+        assert not (gelu_in and stride != 1)
+        wk = np.zeros((9, c_buf), np.float32)
+        wk[:, :c] = wt.reshape(c, 9).T
+        bk = np.zeros(c_buf, np.float32)
+        if bias is not None:
+            bk[:c] = np.asarray(bias, np.float32)
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        out = self.buf(ho, wo, c_buf)
+        w_off = self._add_blob(wk)
+        b_off = self._add_blob(bk)
+        self.vops.append(dict(type=L.PP_OP_DWCONV3X3, in_=x, out=out, res1=-1, res2=-1, cin=c_buf, cout=c_buf, kh=3, kw=3,
+                              stride=stride, pad_h=1, pad_w=1, dil_h=1, dil_w=1, relu=act, up_log2=0, out_nchw=0, res1_shift=0,
+                              res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=L.PP_DW_GELU_IN if gelu_in else 0, w_off=w_off,
+                              b_off=b_off, name=name, flops=2.0 * ho * wo * c * 9))
+        return out
+
+    def layernorm(self, x, gamma, beta, *, eps=1e-6, name="layernorm") -> int:
+        """LayerNorm over the channels of every pixel.  gamma / beta: [c_real], c_real <= the buffer's channels; the padding
+        channels of the output are exact zeros."""
+        h, w, c_buf = self.dims(x)
+        g = np.asarray(gamma, np.float32).reshape(-1)
+        c = g.size
+        assert 0 < c <= c_buf and c_buf % 4 == 0 and c_buf <= 1024, (c, c_buf)
+        gk = np.zeros(c_buf, np.float32)
+        gk[:c] = g
+        bk = np.zeros(c_buf + 1, np.float32)
+        bk[:c] = np.asarray(beta, np.float32).reshape(-1)
+        bk[c_buf] = eps
+        out = self.buf(h, w, c_buf)
+        w_off = self._add_blob(gk)
+        b_off = self._add_blob(bk)
+        self.vops.append(dict(type=L.PP_OP_LAYERNORM, in_=x, out=out, res1=-1, res2=-1, cin=c, cout=c_buf, kh=1, kw=1, stride=1,
+                              pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
+                              out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, flops=8.0 * h * w * c))
+        return out
+
+    def window_attention(self, qkv, table, qkv_bias, *, c_real, heads, window=7, name="window_attn") -> int:
+        """7x7 window attention on a qkv map [h][w][3 * c_buf] (channel s * c_buf + head * hd + d; a 1x1 convolution of the
+        LayerNorm output writes it).  table: relative_position_bias_table [169][heads]; qkv_bias: the Linear's bias [3 * c_real]
+        in torch order (q | k | v) -- what a padded token's k and v are.  Returns [h][w][c_buf]."""
+        h, w, c3 = self.dims(qkv)
+        c_buf = c3 // 3
+        assert c3 == 3 * c_buf and c_buf % 4 == 0 and c_real <= c_buf and c_real % heads == 0 and window == 7, (c3, c_real, heads)
+        tb = np.asarray(table, np.float32)
+        assert tb.shape == ((2 * window - 1) ** 2, heads), tb.shape
+        bq = np.zeros((3, c_buf), np.float32)
+        bq[:, :c_real] = np.asarray(qkv_bias, np.float32).reshape(3, c_real)
+        out = self.buf(h, w, c_buf)
+        w_off = self._add_blob(tb)
+        b_off = self._add_blob(bq)
+        t = window * window
+        n_win = -(-h // window) * -(-w // window)
+        self.vops.append(dict(type=L.PP_OP_WINDOW_ATTN, in_=qkv, out=out, res1=-1, res2=-1, cin=c_real, cout=c_buf, kh=window,
+                              kw=window, stride=heads, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
+                              res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name,
+                              flops=2.0 * n_win * 2 * t * t * c_real))
+        return out
+
+    def gelu_add(self, x, *, res1=-1, name="gelu_add") -> int:
+        """out = res1 + gelu(x)  (res1 = -1: gelu(x))"""
+        h, w, c = self.dims(x)
+        assert c % 4 == 0 and (res1 < 0 or self.dims(res1) == (h, w, c))
+        out = self.buf(h, w, c)
+        self.vops.append(dict(type=L.PP_OP_GELU_ADD, in_=x, out=out, res1=res1, res2=-1, cin=c, cout=c, kh=1, kw=1, stride=1, pad_h=0,
+                              pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0, out_c_off=0,
+                              in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, flops=0.0))
+        return out
+
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
         a 4-term gather (PP_OP_DECONV_BF16).  weight: torch ConvTranspose2d layout [cin][cout][4][4], BN already folded."""

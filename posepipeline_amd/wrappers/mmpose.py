@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib, ops, weights
-from ..models import hrnet, vitpose
+from ..models import hrformer, hrnet, vitpose
 from ..program import Net
 from ..video import open_video
 
@@ -48,6 +48,10 @@ _METHODS = {
     # BASELINE.json configs[0-1] name the W32 256x192 member of the family (mmpose's plain W32 config decodes 'default')
     "HRNet_W32_COCO": (hrnet.hrnet_w32_256x192, "mmpose/checkpoints/hrnet_w32_coco_256x192-c78dce93_20200708.pth",
                        17, hrnet.COCO_FLIP_PAIRS, "default", 11),
+    # TopDownMethodLookup row 3 "MMPoseHrformerCoco" (wrappers/mmpose.py:37-40; 3rdparty/mmpose/config/top_down/hrformer_base_coco_384x288.py:
+    # flip_test, post_process 'default', shift_heatmap, modulate_kernel 17).  The module internals are an unpinned restatement
+    "HRFormer_COCO": (hrformer.hrformer_base_384x288, "mmpose/checkpoints/hrformer_base_coco_384x288-ecf0758d_20220316.pth",
+                      17, hrnet.COCO_FLIP_PAIRS, "default", 17),
     # BASELINE.json configs[4]; NOT a method of the reference wrapper (ViTPose is absent from /root/reference): the
     # published ViTPose COCO configs (UDP crop / DARK-UDP decode, modulate kernel 11, no heatmap shift), bf16 MFMA encoder
     "ViTPose_H_COCO": (vitpose.vitpose_huge, "mmpose/checkpoints/vitpose-h.pth", 17, hrnet.COCO_FLIP_PAIRS, "udp", 11),
@@ -80,6 +84,10 @@ def _model(method, device=0):
             sd = weights.get_state_dict(ckpt, vitpose.vitpose_param_shapes(spec), seed=1,
                                         synth=lambda shapes, seed: vitpose.synth_params(spec, seed))
             prog = vitpose.build_vitpose_program(spec, sd)
+        elif isinstance(spec, hrformer.HRFormerSpec):
+            sd = weights.get_state_dict(ckpt, hrformer.hrformer_param_shapes(spec), seed=1,
+                                        synth=lambda shapes, seed: hrformer.synth_params(spec, seed))
+            prog = hrformer.build_hrformer_program(spec, sd)
         else:
             sd = weights.get_state_dict(ckpt, hrnet.hrnet_param_shapes(spec), seed=1)
             prog = hrnet.build_hrnet_program(spec, sd)
