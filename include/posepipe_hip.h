@@ -576,6 +576,29 @@ int pp_detector_enable_margins(pp_detector* d, int enable, float score_weight);
 /* margins [n_frames][PP_DET_N_MARGINS] of the most recent pp_detector_run (n_frames = that run's) */
 int pp_detector_margins(pp_detector* d, int n_frames, float* margins);
 
+/* Regression of caller-supplied boxes through the RoI head (Tracktor's track propagation: mmtrack TracktorTracker.regress_tracks ->
+ * roi_head.simple_test_bboxes(rescale=True) with rcnn_test_cfg None).  Valid after a COLLECTED pass that contained `frame` and
+ * before the next pass (the frame's FPN maps are resident in the image program's buffers); 0 < n <= the detector's RoI capacity
+ * (1000).  boxes_src_px: host [n][4] x1 y1 x2 y2 in source pixels; they are multiplied by the detector's scale factor (float32),
+ * mapped to their FPN level and RoI-aligned like proposals, run through the RoI program with batch n, decoded (delta2bbox, no
+ * clipping) and divided by the scale factor.  out_boxes host [n][4], out_scores host [n] (foreground softmax): row i belongs to
+ * input row i -- no score threshold and no NMS.  Synchronises the ctx stream.  The pass's own outputs are not touched. */
+int pp_detector_regress(pp_detector* d, int frame, const float* boxes_src_px, int n, float* out_boxes, float* out_scores);
+
+/* ---- ECC image alignment (camera-motion compensation of the Tracktor configuration; csrc/ecc.hip) -----------------------
+ * pp_gray_from_nhwc4: gray = (0.299 x[r] + 0.587 x[g]) + 0.114 x[b] in float32 (cv2.COLOR_RGB2GRAY on a float image) of a device
+ *   [n][h][w][4] tensor -> device [n][h][w]; queued on the ctx stream, no synchronisation.
+ * pp_ecc_euclidean: cv2.findTransformECC(template, input, identity, MOTION_EUCLIDEAN, (num_iters, stop_eps), None, 1) of n_pairs
+ *   image pairs at once (the algorithm is restated in csrc/ecc.hip).  gray: device [n_images][h][w] float32 (NOT inside the ctx
+ *   scratch); pairs: host [n_pairs][2] = (template image, input image).  Outputs (host): warp [n_pairs][6] row-major 2 x 3 map in
+ *   float64, rho [n_pairs], iters [n_pairs] loop bodies executed, status [n_pairs] PP_ECC_*.  A pair whose status is not PP_ECC_OK
+ *   (OpenCV raises cv2.error there) keeps the map it had when the failing iteration began; the other pairs are unaffected.
+ *   Deterministic: two calls on the same inputs return the same bits.  One stream synchronisation, at the end. */
+enum { PP_ECC_OK = 0, PP_ECC_NAN = 1 /* rho is NaN */, PP_ECC_DIVERGED = 2 /* non-positive denominator of lambda */ };
+int pp_gray_from_nhwc4(pp_ctx* ctx, const float* x_nhwc4, int n, int h, int w, int r, int g, int b, float* gray);
+int pp_ecc_euclidean(pp_ctx* ctx, const float* gray, int n_images, int h, int w, const int32_t* pairs, int n_pairs, int num_iters,
+                     double stop_eps, double* warp, double* rho, int32_t* iters, int32_t* status);
+
 /* ---- DeepSortYOLOv4 pre / post-processing ------------------------------------------------------------
  * tracking_method 0 (pipeline.py:519-523 -> wrappers/deep_sort_yolov4/parser.py:21): YOLOv4 detector + mars-small128
  * appearance encoder + the in-tree DeepSORT tracker (pp_tracker mode 0).  The two networks are layer programs

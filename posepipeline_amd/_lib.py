@@ -26,6 +26,7 @@ PP_ACT_GELU = 7          # PP_OP_DWCONV3X3 only
 PP_DW_GELU_IN = 1        # pp_op.pad_end of a PP_OP_DWCONV3X3
 PP_NET_NUMERICS_DEFAULT, PP_NET_NUMERICS_EXACT, PP_NET_NUMERICS_SPLIT = 0, 1, 2
 PP_NET_NUMERICS_SPLIT_BF16, PP_NET_NUMERICS_SPLIT_F16 = 3, 4
+PP_ECC_OK, PP_ECC_NAN, PP_ECC_DIVERGED = 0, 1, 2
 # "split": the form pp_conv_split_kind / POSEPIPE_SPLIT_F16 select when the net is created; the two forms by name
 NUMERICS = {None: 0, "default": 0, "exact": 1, "split": 2, "split_bf16": 3, "split_f16": 4}
 
@@ -143,6 +144,9 @@ SIGNATURES = {
     "pp_detector_collect": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "pp_detector_enable_margins": (_i, [_vp, _i, C.c_float]),
     "pp_detector_margins": (_i, [_vp, _i, _vp]),
+    "pp_detector_regress": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "pp_gray_from_nhwc4": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "pp_ecc_euclidean": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp]),
     "pp_nms": (_i, [_vp, _vp, _vp, _i, C.c_double, _i, _vp, C.POINTER(C.c_int32), _i]),
     "pp_videopose3d_lift": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "pp_videopose3d_lift_many": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i]),

@@ -53,6 +53,9 @@ struct pp_detector {
     int32_t *h_ndets = nullptr, *h_nprops = nullptr;
     hipEvent_t ev_done = nullptr;
     int pending_frames = 0;      // > 0: a pass is in flight (enqueued, not collected)
+    int resident_frames = 0;     // frames of the last COLLECTED pass: their FPN maps are what pp_detector_regress reads
+    float *reg_rois = nullptr, *reg_boxes = nullptr, *reg_scores = nullptr;   // pp_detector_regress: [max_rois] rows each
+    int32_t *reg_n = nullptr, *reg_n_out = nullptr;
     bool pending_props = false;
     float ms[6];
     hipEvent_t ev[7];
@@ -229,7 +232,8 @@ int pp_detector_create(pp_net* netA, pp_net* netB, const int32_t* bufs_a, const 
                  o_od = carve((size_t)F * d->max_det * 20), o_no = carve((size_t)F * 4),
                  o_s1 = carve(pp_nms_batched_scratch_bytes(d->max_n, F)), o_s2 = carve(pp_nms_batched_scratch_bytes(d->max_rois, F)),
                  o_mg = carve((size_t)F * PP_DET_N_MARGINS * 4), o_cg = carve((size_t)F * 5 * 4), o_k1 = carve((size_t)F * d->max_n),
-                 o_kf2 = carve((size_t)F * d->max_rois);
+                 o_kf2 = carve((size_t)F * d->max_rois), o_rr = carve((size_t)d->max_rois * 16), o_rb = carve((size_t)d->max_rois * 16),
+                 o_rsc = carve((size_t)d->max_rois * 4), o_rn = carve(4), o_rno = carve(4);
     PP_HIP_CHECK(hipMalloc((void**)&d->d_work, off));
     PP_HIP_CHECK(hipMemset(d->d_work, 0, off));
     char* base = d->d_work;
@@ -243,6 +247,8 @@ int pp_detector_create(pp_net* netA, pp_net* netB, const int32_t* bufs_a, const 
     d->nms_scratch1 = base + o_s1; d->nms_scratch2 = base + o_s2;
     d->d_margins = (float*)(base + o_mg); d->cut_gap = (float*)(base + o_cg);
     d->kflag1 = (unsigned char*)(base + o_k1); d->kflag2 = (unsigned char*)(base + o_kf2);
+    d->reg_rois = (float*)(base + o_rr); d->reg_boxes = (float*)(base + o_rb); d->reg_scores = (float*)(base + o_rsc);
+    d->reg_n = (int32_t*)(base + o_rn); d->reg_n_out = (int32_t*)(base + o_rno);
     d->h_margins.assign((size_t)F * PP_DET_N_MARGINS, 0.f);
     for (auto& e : d->ev) PP_HIP_CHECK(hipEventCreate(&e));
     PP_HIP_CHECK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
@@ -273,6 +279,7 @@ int pp_detector_enqueue(pp_detector* d, const uint8_t* frames, int n_frames, int
     PP_REQUIRE(d, "pp_detector_enqueue: detector is NULL");
     PP_REQUIRE(n_frames > 0 && n_frames <= d->max_frames, "pp_detector_enqueue: %d frames not in (0, %d]", n_frames, d->max_frames);
     PP_REQUIRE(d->pending_frames == 0, "pp_detector_enqueue: the previous pass has not been collected");
+    d->resident_frames = 0;
     float* dets = d->h_dets;
     int32_t* n_dets = d->h_ndets;
     float* proposals = want_proposals ? d->h_props : nullptr;
@@ -407,6 +414,7 @@ int pp_detector_collect(pp_detector* d, float* dets, int32_t* n_dets, float* pro
     const int F = d->pending_frames;
     PP_HIP_CHECK(hipEventSynchronize(d->ev_done));
     d->pending_frames = 0;
+    d->resident_frames = F;
     memcpy(dets, d->h_dets, (size_t)F * d->max_det * 5 * sizeof(float));
     memcpy(n_dets, d->h_ndets, (size_t)F * sizeof(int32_t));
     if (proposals) memcpy(proposals, d->h_props, (size_t)F * d->max_rois * 16);
@@ -423,6 +431,57 @@ int pp_detector_run(pp_detector* d, const uint8_t* frames, int n_frames, int fra
     int rc = pp_detector_enqueue(d, frames, n_frames, frames_mem, proposals || n_proposals);
     if (rc != PP_OK) return rc;
     return pp_detector_collect(d, dets, n_dets, proposals, n_proposals);
+}
+
+// Tracktor's regress_tracks: the RoI head on caller-supplied boxes of one frame of the last collected pass.  The launchers are the
+// pass's own (RoI level mapping + RoIAlign, the RoI program, softmax + delta2bbox + rescale), called for one "frame" whose FPN maps
+// start at `frame` and whose RoI capacity is n, with a score threshold no score can miss: the ordered compaction of the final decode
+// then keeps every row in place.
+int pp_detector_regress(pp_detector* d, int frame, const float* boxes_src_px, int n, float* out_boxes, float* out_scores) {
+    PP_REQUIRE(d && boxes_src_px && out_boxes && out_scores, "pp_detector_regress: NULL argument");
+    PP_REQUIRE(d->pending_frames == 0, "pp_detector_regress: a pass is in flight (collect it first)");
+    PP_REQUIRE(frame >= 0 && frame < d->resident_frames, "pp_detector_regress: frame %d is not one of the %d frames of the last collected pass",
+               frame, d->resident_frames);
+    PP_REQUIRE(n > 0 && n <= d->max_rois, "pp_detector_regress: %d boxes not in (0, %d]", n, d->max_rois);
+    hipStream_t s = d->ctx->stream;
+    PpRange range("det.regress");
+    std::vector<float> rois((size_t)n * 4);
+    for (int i = 0; i < n; ++i) {
+        rois[4 * i] = boxes_src_px[4 * i] * d->sfx; rois[4 * i + 1] = boxes_src_px[4 * i + 1] * d->sfy;
+        rois[4 * i + 2] = boxes_src_px[4 * i + 2] * d->sfx; rois[4 * i + 3] = boxes_src_px[4 * i + 3] * d->sfy;
+    }
+    const int32_t n32 = n;
+    PP_HIP_CHECK(hipMemcpyAsync(d->reg_rois, rois.data(), rois.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    PP_HIP_CHECK(hipMemcpyAsync(d->reg_n, &n32, sizeof(n32), hipMemcpyHostToDevice, s));
+    DetFpnArgs fa{};
+    for (int l = 0; l < 4; ++l) {
+        void* p;
+        pp_net_buffer(d->netA, d->fpn_buf[l], &p, nullptr);
+        fa.feat[l] = (const float*)p + (size_t)frame * d->lvl_h[l] * d->lvl_w[l] * 256;
+        fa.h[l] = d->lvl_h[l]; fa.w[l] = d->lvl_w[l]; fa.stride[l] = d->lvl_stride[l];
+    }
+    fa.c = 256;
+    void *roi_in_ptr, *pcls, *preg;
+    pp_net_buffer(d->netB, d->roi_in, &roi_in_ptr, nullptr);
+    pp_net_buffer(d->netB, d->roi_cls, &pcls, nullptr);
+    pp_net_buffer(d->netB, d->roi_reg, &preg, nullptr);
+    int rc = det_enqueue_roi_align(s, fa, d->reg_rois, d->reg_n, n, (float*)roi_in_ptr, 1, pp_net_numerics(d->netB) == PP_NET_NUMERICS_SPLIT,
+                                   d->roi_amax);
+    if (rc != PP_OK) return rc;
+    if (d->roi_amax) {
+        void* am = nullptr;
+        rc = pp_net_input_amax(d->netB, d->roi_in, &am);
+        if (rc != PP_OK) return rc;
+    }
+    rc = pp_net_run(d->netB, n, 0, -1);
+    if (rc != PP_OK) return rc;
+    rc = det_enqueue_final_decode(s, d->reg_rois, d->reg_n, n, (const float*)pcls, (const float*)preg, d->sfx, d->sfy, -1.f, d->reg_boxes,
+                                  d->reg_scores, d->reg_n_out, 1);
+    if (rc != PP_OK) return rc;
+    PP_HIP_CHECK(hipMemcpyAsync(out_boxes, d->reg_boxes, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+    PP_HIP_CHECK(hipMemcpyAsync(out_scores, d->reg_scores, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    PP_HIP_CHECK(hipStreamSynchronize(s));     // `rois` and `n32` must outlive their copies, and the results are complete on return
+    return PP_OK;
 }
 
 int pp_detector_enable_margins(pp_detector* d, int enable, float score_weight) {

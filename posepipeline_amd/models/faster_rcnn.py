@@ -299,6 +299,17 @@ class Detector:
             return out, [props[i, : nprops[i]].copy() for i in range(f)]
         return out
 
+    def regress(self, frame, boxes):
+        """Tracktor's track propagation: boxes [n][4] float32 (source pixels) through the RoI head on frame `frame` of the last
+        collected pass (its FPN maps are still resident) -> (boxes [n][4], scores [n]); row i belongs to input row i, no score
+        threshold, no NMS (pp_detector_regress).  n <= MAX_ROIS."""
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+        n = len(boxes)
+        out, scores = np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+        if n:
+            L.check(self.ctx.lib.pp_detector_regress(self.handle, int(frame), L.ptr(boxes), n, L.ptr(out), L.ptr(scores)), "pp_detector_regress")
+        return out, scores
+
     def timing(self):
         ms = np.zeros(6, np.float32)
         L.check(self.ctx.lib.pp_detector_timing(self.handle, L.ptr(ms)), "pp_detector_timing")

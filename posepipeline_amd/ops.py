@@ -146,3 +146,21 @@ class TopDown:
         ms = np.zeros(3, np.float32)
         L.check(self.ctx.lib.pp_topdown_timing(self.handle, L.ptr(ms)), "pp_topdown_timing")
         return tuple(float(v) for v in ms)
+
+
+def gray_from_nhwc4(ctx: L.Context, src_dev: int, n: int, h: int, w: int, gray_dev: int, rgb=(0, 1, 2)):
+    """cv2.COLOR_RGB2GRAY of a device [n][h][w][4] float32 tensor into device [n][h][w] (queued on the ctx stream)"""
+    L.check(ctx.lib.pp_gray_from_nhwc4(ctx.handle, C.c_void_p(src_dev), n, h, w, rgb[0], rgb[1], rgb[2], C.c_void_p(gray_dev)),
+            "pp_gray_from_nhwc4")
+
+
+def ecc_euclidean(ctx: L.Context, gray_dev: int, n_images: int, h: int, w: int, pairs, num_iters=100, stop_eps=1e-5):
+    """cv2.findTransformECC(MOTION_EUCLIDEAN) of every (template image, input image) pair of device [n_images][h][w] float32 gray
+    images in one call (csrc/ecc.hip) -> (warp [n_pairs][2][3] float64, rho [n_pairs], iterations [n_pairs], status [n_pairs] PP_ECC_*)"""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    k = len(pairs)
+    warp, rho = np.zeros((k, 2, 3), np.float64), np.zeros(k, np.float64)
+    iters, status = np.zeros(k, np.int32), np.zeros(k, np.int32)
+    L.check(ctx.lib.pp_ecc_euclidean(ctx.handle, C.c_void_p(gray_dev), n_images, h, w, L.ptr(pairs), k, int(num_iters), float(stop_eps),
+                                     L.ptr(warp), L.ptr(rho), L.ptr(iters), L.ptr(status)), "pp_ecc_euclidean")
+    return warp, rho, iters, status

@@ -378,3 +378,135 @@ class SortReidTracker:
         for i in [i for i, t in self.tracks.items() if fid - t["last"] >= self.retain or (t["tentative"] and t["last"] != fid)]:
             del self.tracks[i]
         return np.concatenate([ids[:, None].astype(np.float32), dets], axis=1).astype(np.float32) if n else np.zeros((0, 6), np.float32)
+
+
+# ---- mmtrack TracktorTracker (method "tracktor" of wrappers/mmtrack.py) ---------------------------------------------------
+def _nms_f32(boxes, scores, iou_thr):
+    """mmcv `nms` on the host (float32, x1y1x2y2, area = w * h, suppress where inter > thr * union, stable descending score
+    order): kept indices.  The few boxes of a frame's tracks; the detector's own NMS is the device kernel (nms.hip)."""
+    b, s = np.asarray(boxes, np.float32).reshape(-1, 4), np.asarray(scores, np.float32).reshape(-1)
+    order = np.argsort(-s, kind="stable")
+    b = b[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    thr, dead, keep = np.float32(iou_thr), np.zeros(len(b), bool), []
+    for i in range(len(b)):
+        if dead[i]:
+            continue
+        keep.append(int(order[i]))
+        w = np.maximum(np.minimum(b[i, 2], b[i + 1:, 2]) - np.maximum(b[i, 0], b[i + 1:, 0]), np.float32(0))
+        h = np.maximum(np.minimum(b[i, 3], b[i + 1:, 3]) - np.maximum(b[i, 1], b[i + 1:, 1]), np.float32(0))
+        inter = w * h
+        dead[i + 1:] |= inter > thr * ((area[i] + area[i + 1:]) - inter)
+    return keep
+
+
+def warp_boxes_f32(boxes, warp):
+    """CameraMotionCompensation.warp_bboxes: the tl and br corners of [n][4] float32 boxes through the 2 x 3 map, in float32
+    ((m00 x + m01 y) + m02; cv2.findTransformECC returns a float32 matrix, so the map is rounded to float32 first)"""
+    b = np.asarray(boxes, np.float32).reshape(-1, 4)
+    m = np.asarray(warp, np.float64).reshape(2, 3).astype(np.float32)
+    out = np.empty_like(b)
+    for k in (0, 2):
+        out[:, k] = (m[0, 0] * b[:, k] + m[0, 1] * b[:, k + 1]) + m[0, 2]
+        out[:, k + 1] = (m[1, 0] * b[:, k] + m[1, 1] * b[:, k + 1]) + m[1, 2]
+    return out
+
+
+class TracktorTracker:
+    """mmtrack 0.x `TracktorTracker.track` (+ BaseTracker's memo, CameraMotionCompensation.warp_bboxes) as configured by
+    3rdparty/mmtracking/mot/tracktor/tracktor_faster-rcnn_r50_fpn_4e_mot17-private-half.py:43-62: obj_score_thr .5, regression
+    (obj_score_thr .5, nms IoU .6, match_iou_thr .3), reid (obj_score_thr .5, img_scale (256, 128), match_score_thr 2.0,
+    match_iou_thr .2), momentums None, num_frames_retain 10; motion = camera-motion compensation only (no linear motion model, so
+    one box per track is warped).  Per frame:
+
+      detections with score > .5 are kept.  No track yet: each starts a track (ids from a running counter) and is embedded.
+      Otherwise  1. every track's last box is warped with the frame's ECC map (warp_boxes_f32);
+                 2. the boxes of the tracks seen in the PREVIOUS frame are regressed through the detector's RoI head on this frame;
+                    NMS (IoU .6) over those with score > 0, result in descending score order; score > .5 survives: propagated;
+                 3. detections whose IoU with any propagated box is >= .3 are dropped;
+                 4. propagated boxes and remaining detections are embedded; every track that was NOT propagated is a candidate for
+                    the remaining detections: cost = Euclidean distance of the mean of its last <= 10 embeddings to the detection's,
+                    1e6 where the IoU of its (warped) last box with the detection is < .2; Hungarian; cost <= 2.0 hands the id over;
+                 5. the rest start new tracks, in detector order.
+      Rows out: propagated first, then detections, [id, x1, y1, x2, y2, score].  Every row updates (or starts) its track with box,
+      score, embedding and frame; tracks not seen for 10 frames are dropped.  frame_id 0 resets the tracker.
+
+    The three device-side pieces come in as arguments, so the flow runs without a GPU:
+      regress(boxes [n][4] float32) -> (boxes [n][4], scores [n])     Detector.regress on the current frame
+      embed(boxes [n][4] float32)   -> [n][d] float32                  ReidEncoder.encode on the current frame
+      warp                          2 x 3 map of the frame (pp_ecc_euclidean); only read when there are tracks
+    The map is estimated between the detector's INPUT tensors (normalised, resized, padded) and applied to boxes in SOURCE pixels:
+    that is how the configuration behaves with rescale=True.  mmtrack is not vendored: restated from memory, PARITY UNPINNED
+    (tests/tracktor_ref.py holds the loop-by-loop transcription this class is tested against)."""
+
+    def __init__(self, obj_score_thr=0.5, regress_score_thr=0.5, regress_nms_iou=0.6, regress_match_iou=0.3, reid_match_score=2.0,
+                 reid_match_iou=0.2, num_samples=10, num_frames_retain=10):
+        self.lib = L.load_library()
+        self.obj_score_thr, self.reg_thr, self.reg_nms = np.float32(obj_score_thr), np.float32(regress_score_thr), regress_nms_iou
+        self.reg_iou, self.reid_score, self.reid_iou = np.float32(regress_match_iou), reid_match_score, np.float32(reid_match_iou)
+        self.num_samples, self.retain = num_samples, num_frames_retain
+        self.reset()
+
+    def reset(self):
+        self.tracks: dict = {}      # id -> dict(box, score, last, embeds); insertion-ordered like mmtrack's memo
+        self.num_tracks = 0
+
+    def live_ids(self) -> set:
+        return set(self.tracks)
+
+    def step(self, frame_id, dets, regress, embed, warp=None):
+        """dets [n][5] float32 (x1, y1, x2, y2, score) -> rows [m][6] float32 (id, x1, y1, x2, y2, score)"""
+        if frame_id == 0:
+            self.reset()
+        dets = np.asarray(dets, np.float32).reshape(-1, 5)
+        dets = dets[dets[:, 4] > self.obj_score_thr]
+        if not self.tracks:
+            boxes, scores = dets[:, :4], dets[:, 4]
+            ids = np.arange(self.num_tracks, self.num_tracks + len(dets), dtype=np.int64)
+        else:
+            order = list(self.tracks)
+            warped = warp_boxes_f32(np.stack([self.tracks[i]["box"] for i in order]), warp)
+            for i, b in zip(order, warped):
+                self.tracks[i]["box"] = b
+            prev = [i for i in order if self.tracks[i]["last"] == frame_id - 1]
+            p_ids, p_boxes, p_scores = np.zeros(0, np.int64), np.zeros((0, 4), np.float32), np.zeros(0, np.float32)
+            if prev:
+                rb, rs = regress(np.stack([self.tracks[i]["box"] for i in prev]))
+                rb, rs = np.asarray(rb, np.float32).reshape(-1, 4), np.asarray(rs, np.float32).reshape(-1)
+                valid = np.flatnonzero(rs > np.float32(0))
+                keep = valid[_nms_f32(rb[valid], rs[valid], self.reg_nms)] if len(valid) else valid
+                keep = keep[rs[keep] > self.reg_thr]
+                p_ids, p_boxes, p_scores = np.asarray(prev, np.int64)[keep], rb[keep], rs[keep]
+            if len(p_ids) and len(dets):
+                dets = dets[~(_iou_f32(p_boxes, dets[:, :4]) >= self.reg_iou).any(axis=0)]
+            d_ids = np.full(len(dets), -1, np.int64)
+            boxes, scores = np.concatenate([p_boxes, dets[:, :4]]), np.concatenate([p_scores, dets[:, 4]])
+        embeds = np.asarray(embed(boxes), np.float32).reshape(len(boxes), -1) if len(boxes) else np.zeros((0, 1), np.float32)
+        if self.tracks:
+            cand = [i for i in order if i not in set(p_ids.tolist())]
+            if cand and len(dets):
+                means = []
+                for i in cand:
+                    e = self.tracks[i]["embeds"][-self.num_samples:]
+                    acc = np.zeros_like(e[0])
+                    for v in e:
+                        acc = (acc + v).astype(np.float32)
+                    means.append((acc / np.float32(len(e))).astype(np.float32))
+                cost = reid_cdist(np.stack(means), embeds[len(p_ids):]).astype(np.float64)
+                cost[_iou_f32(np.stack([self.tracks[i]["box"] for i in cand]), dets[:, :4]) < self.reid_iou] = REID_GATED
+                for r, c in zip(*linear_sum_assignment(cost)):
+                    if cost[r, c] <= self.reid_score:
+                        d_ids[c] = cand[r]
+            new = d_ids == -1
+            d_ids[new] = np.arange(self.num_tracks, self.num_tracks + int(new.sum()))
+            ids = np.concatenate([p_ids, d_ids])
+        self.num_tracks = max(self.num_tracks, int(ids.max()) + 1) if len(ids) else self.num_tracks
+        for i, b, s, e in zip(ids.tolist(), boxes, scores, embeds):
+            t = self.tracks.setdefault(i, dict(embeds=[]))
+            t["box"], t["score"], t["last"] = b.copy(), s, frame_id
+            t["embeds"] = (t["embeds"] + [e.copy()])[-self.num_samples:]
+        for i in [i for i, t in self.tracks.items() if frame_id - t["last"] >= self.retain]:
+            del self.tracks[i]
+        if len(ids) == 0:
+            return np.zeros((0, 6), np.float32)
+        return np.concatenate([ids[:, None].astype(np.float32), boxes, scores[:, None]], axis=1).astype(np.float32)
