@@ -653,6 +653,51 @@ int pp_videopose3d_lift_many(pp_net* net, int in_buf, int out_buf, const float* 
 int pp_videopose3d_lift(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, int n_frames,
                         int in_features, int out_features, int pad, float* out);
 
+/* ---- bottom-up stage (crop_affine.hip, bottomup.hip) -------------------------------------------------
+ * HigherHRNet + associative embedding as mmpose 0.x runs it for `mmpose_bottom_up` (wrappers/mmpose.py:84-121; test_cfg of
+ * 3rdparty/mmpose/config/bottom_up/higherhrnet/coco/higher_hrnet48_coco_512x512.py).  mmpose is not vendored: the rules below
+ * are an UNPINNED restatement.
+ *
+ * pp_warp_affine_normalize: the sibling of pp_crop_affine_normalize for a transform given by (center, scale) directly
+ * (BottomUpResizeAlign: cv2.warpAffine(frame, get_affine_transform(center, scale, 0, (out_w, out_h)), (out_w, out_h)), the same
+ * fixed-point bilinear warp, then the 3x256 normalisation table).  center / scale: host double[2], scale in units of 200 px;
+ * every frame is warped with the same transform.  out: [n_out][out_h][out_w][4]; with flip != 0, n_out = 2 * n_frames and sample
+ * n_frames + i is sample i mirrored in W.  warp_u8 (optional): [n_frames][out_h][out_w][3].  mem: where frames / out / warp_u8 live.
+ *
+ * The three post-processing calls share these arguments, all maps DEVICE pointers, NCHW fp32:
+ *   s0 [2 * n_frames][2 * k][h0][w0]: the first output of the network (channels 0 .. k-1 heat-maps, k .. 2k-1 tags), sample
+ *      n_frames + i computed from the mirrored input of sample i;  s1 [2 * n_frames][k][h1][w1]: the second (heat-maps only);
+ *   flip_perm: host [k], the left / right channel permutation; (hr, wr): the size the maps are projected to;
+ *   align_corners: of the bilinear resize (torch F.interpolate semantics, evaluated in float32).
+ * A mirrored map is read at column w - 1 - x and channel flip_perm[c] BEFORE it is resized.
+ *   heat-map:  hm[f][c] = ((((0 + R(s0[f][c])) + R(s1[f][c])) + R(flip s0[n_frames + f])) + R(flip s1[n_frames + f])) / 4
+ *   tags:      tag[f][c][0] = R(s0[f][k + c]),  tag[f][c][1] = R(flip s0[n_frames + f] tag channel)
+ * pp_bottomup_aggregate writes hm [n_frames][k][hr][wr].  The tags are never stored: the two other calls evaluate them where
+ * they need them, through the same device function, so the values are bit-equal across calls.
+ *
+ * pp_bottomup_candidates (HeatmapParser.nms + top_k): a pixel survives when no pixel of its 5x5 neighbourhood (clipped to the map)
+ * is larger.  Per frame and joint the max_people (<= 64) largest survivors with a value > 0 are returned in descending order;
+ * EQUAL VALUES RANK BY THE LOWER FLAT INDEX y * wr + x (torch.topk leaves that order unspecified).  cand: host
+ * [n_frames][k][max_people][8] fp32 = (val, x, y, tag0, tag1, hm[min(hr-1, y+1)][x] > hm[max(0, y-1)][x],
+ * hm[y][min(wr-1, x+1)] > hm[y][max(0, x-1)], flat index); unused slots are (0, -1, -1, 0, 0, 0, 0, -1).  (torch fills such
+ * slots with zero-valued pixels; the parser drops every candidate whose value is not above detection_threshold > 0.)
+ *
+ * pp_bottomup_refine (HeatmapParser.refine), all persons of a chunk in one call: for person p (of frame person_frame[p], mean
+ * tag mean_tag[p][2]) and every joint c with need[p * k + c] != 0:  the first index of the maximum over the map of
+ * hm - rint(sqrt((tag0 - m0)^2 + (tag1 - m1)^2)), in float32.  out: host [n_person][k][4] fp32 = (x, y, hm value there,
+ * bits: 1 = the y comparison above, 2 = the x comparison); rows with need == 0 are zeros.
+ */
+int pp_warp_affine_normalize(pp_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const double* center,
+                             const double* scale, int out_w, int out_h, const float* lut, const int32_t* chan_map,
+                             int flip, float* out, uint8_t* warp_u8, int mem);
+int pp_bottomup_aggregate(pp_ctx* ctx, const float* s0, const float* s1, int n_frames, int k, int h0, int w0, int h1,
+                          int w1, const int32_t* flip_perm, int hr, int wr, int align_corners, float* hm);
+int pp_bottomup_candidates(pp_ctx* ctx, const float* hm, const float* s0, int n_frames, int k, int h0, int w0,
+                           const int32_t* flip_perm, int hr, int wr, int align_corners, int max_people, float* cand);
+int pp_bottomup_refine(pp_ctx* ctx, const float* hm, const float* s0, int n_frames, int k, int h0, int w0,
+                       const int32_t* flip_perm, int hr, int wr, int align_corners, int n_person,
+                       const int32_t* person_frame, const float* mean_tag, const int32_t* need, float* out);
+
 #ifdef __cplusplus
 }
 #endif

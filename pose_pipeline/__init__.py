@@ -14,7 +14,8 @@ of scope and raises ImportError as an absent module should.
 """
 import os
 
-from posepipeline_amd.pipeline import (BestDetectedFrames, DetectedFrames, HandBbox, HandBboxMethod,  # noqa: F401
+from posepipeline_amd.pipeline import (BestDetectedFrames, BottomUpMethod, BottomUpMethodLookup, BottomUpPeople,  # noqa: F401
+                                       BottomUpPerson, DetectedFrames, HandBbox, HandBboxMethod,  # noqa: F401
                                        HandBboxMethodLookup, HandPoseEstimation, HandPoseEstimationMethod,
                                        HandPoseEstimationMethodLookup, LiftingMethod, LiftingMethodLookup,
                                        LiftingPerson, PersonBbox, PersonBboxValid, TopDownMethod, TopDownMethodLookup,
@@ -33,5 +34,6 @@ MODEL_DATA_DIR = _model_data_dir()
 __all__ = ["Video", "VideoInfo", "TrackingBboxMethodLookup", "TrackingBboxMethod", "TrackingBbox", "PersonBboxValid",
            "PersonBbox", "DetectedFrames", "BestDetectedFrames", "TopDownMethodLookup", "TopDownMethod", "TopDownPerson", "LiftingMethodLookup",
            "LiftingMethod", "LiftingPerson", "HandBboxMethodLookup", "HandBboxMethod", "HandBbox", "HandPoseEstimationMethodLookup",
-           "HandPoseEstimationMethod", "HandPoseEstimation", "MODEL_DATA_DIR", "add_path", "set_environmental_variables",
+           "HandPoseEstimationMethod", "HandPoseEstimation", "BottomUpMethodLookup", "BottomUpMethod", "BottomUpPeople",
+           "BottomUpPerson", "MODEL_DATA_DIR", "add_path", "set_environmental_variables",
            "pytorch_memory_limit", "tensorflow_memory_limit"]

@@ -168,6 +168,10 @@ SIGNATURES = {
     "pp_gemm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i]),
     "pp_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _i]),
     "pp_attention_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "pp_warp_affine_normalize": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "pp_bottomup_aggregate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "pp_bottomup_candidates": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "pp_bottomup_refine": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -192,6 +192,40 @@ bool pp_person_transform(const double* bb, int out_w, int out_h, float cs[4], Pe
     return true;
 }
 
+// mmpose `get_affine_transform(center, scale, 0, (out_w, out_h))` for a (center, scale) given directly (BottomUpResizeAlign) +
+// OpenCV's inversion: the three point pairs are float32, the sums in front of them float64; only scale[0] enters (src_w)
+void pp_center_scale_transform(const double center[2], const double scale[2], int out_w, int out_h, PersonXform* t) {
+    const double src_w = scale[0] * 200.0;
+    const float s0x = (float)center[0], s0y = (float)center[1];
+    const float s1x = (float)(center[0] + 0.0), s1y = (float)(center[1] + src_w * -0.5);
+    const float d0 = s0x - s1x, d1 = s0y - s1y;
+    const float s2x = s1x + (-d1), s2y = s1y + d0;
+    const double dst_w = (double)out_w, dst_h = (double)out_h;
+    const float t0x = (float)(dst_w * 0.5), t0y = (float)(dst_h * 0.5);
+    const float t1x = (float)(dst_w * 0.5 + 0.0), t1y = (float)(dst_h * 0.5 + dst_w * -0.5);
+    const float e0 = t0x - t1x, e1 = t0y - t1y;
+    const float t2x = t1x + (-e1), t2y = t1y + e0;
+    const float sp[3][2] = {{s0x, s0y}, {s1x, s1y}, {s2x, s2y}};
+    const float dp[3][2] = {{t0x, t0y}, {t1x, t1y}, {t2x, t2y}};
+    double A[6][6] = {}, b[6], M[6];
+    for (int i = 0; i < 3; ++i) {
+        A[2 * i][0] = sp[i][0]; A[2 * i][1] = sp[i][1]; A[2 * i][2] = 1.0;
+        A[2 * i + 1][3] = sp[i][0]; A[2 * i + 1][4] = sp[i][1]; A[2 * i + 1][5] = 1.0;
+        b[2 * i] = dp[i][0]; b[2 * i + 1] = dp[i][1];
+    }
+    if (!solve6(A, b, M))
+        for (double& m : M) m = 0.0;
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1.0 / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    t->a00 = M[0]; t->a01 = M[1]; t->b0 = b1;
+    t->a10 = M[3]; t->a11 = M[4]; t->b1 = b2;
+    t->valid = 1;
+}
+
 int pp_enqueue_crop(hipStream_t s, const uint8_t* frames, int h, int w, const PersonXform* xf, int n_person,
                     int out_w, int out_h, const float* lut, const int32_t chan_map[3], int flip, float* out,
                     uint8_t* crop_u8) {
@@ -266,6 +300,54 @@ extern "C" int pp_crop_affine_normalize(pp_ctx* ctx, const uint8_t* frames, int 
         PP_HIP_CHECK(hipMemcpyAsync(out, dout, out_e * 4, hipMemcpyDeviceToHost, s));
         if (crop_u8) PP_HIP_CHECK(hipMemcpyAsync(crop_u8, dcrop, crop_b, hipMemcpyDeviceToHost, s));
     }
+    PP_HIP_CHECK(hipStreamSynchronize(s));
+    return PP_OK;
+}
+
+extern "C" int pp_warp_affine_normalize(pp_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const double* center,
+                                        const double* scale, int out_w, int out_h, const float* lut, const int32_t* chan_map,
+                                        int flip, float* out, uint8_t* warp_u8, int mem) {
+    PP_REQUIRE(ctx && frames && center && scale && lut && chan_map && out, "pp_warp_affine_normalize: NULL argument");
+    PP_REQUIRE(h > 0 && w > 0 && out_w > 0 && out_h > 0, "pp_warp_affine_normalize: empty dims");
+    PP_REQUIRE(mem == PP_MEM_HOST || mem == PP_MEM_DEVICE, "pp_warp_affine_normalize: mem");
+    if (n_frames <= 0) return PP_OK;
+    for (int c = 0; c < 3; ++c) PP_REQUIRE(chan_map[c] >= 0 && chan_map[c] < 3, "chan_map[%d] out of range", c);
+    flip = flip ? 1 : 0;
+    std::vector<PersonXform> xf(n_frames);
+    for (int i = 0; i < n_frames; ++i) {
+        pp_center_scale_transform(center, scale, out_w, out_h, &xf[i]);
+        xf[i].frame = i;
+    }
+    const size_t frames_b = (size_t)n_frames * h * w * 3;
+    const size_t out_e = (size_t)n_frames * (flip ? 2 : 1) * out_w * out_h * 4;
+    const size_t warp_b = warp_u8 ? (size_t)n_frames * out_w * out_h * 3 : 0;
+    size_t need = ScratchCursor::align(n_frames * sizeof(PersonXform)) + ScratchCursor::align(768 * sizeof(float));
+    if (mem == PP_MEM_HOST) need += ScratchCursor::align(frames_b) + ScratchCursor::align(out_e * 4) + ScratchCursor::align(warp_b);
+    int rc = ctx->ensure_scratch(need);
+    if (rc != PP_OK) return rc;
+    ScratchCursor cur(ctx);
+    hipStream_t s = ctx->stream;
+    PersonXform* dxf = cur.take<PersonXform>(n_frames);
+    float* dlut = cur.take<float>(768);
+    PP_HIP_CHECK(hipMemcpyAsync(dxf, xf.data(), n_frames * sizeof(PersonXform), hipMemcpyHostToDevice, s));
+    PP_HIP_CHECK(hipMemcpyAsync(dlut, lut, 768 * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint8_t* dframes = frames;
+    float* dout = out;
+    uint8_t* dwarp = warp_u8;
+    if (mem == PP_MEM_HOST) {
+        uint8_t* df = cur.take<uint8_t>(frames_b);
+        PP_HIP_CHECK(hipMemcpyAsync(df, frames, frames_b, hipMemcpyHostToDevice, s));
+        dframes = df;
+        dout = cur.take<float>(out_e);
+        if (warp_u8) dwarp = cur.take<uint8_t>(warp_b);
+    }
+    rc = pp_enqueue_crop(s, dframes, h, w, dxf, n_frames, out_w, out_h, dlut, chan_map, flip, dout, dwarp);
+    if (rc != PP_OK) return rc;
+    if (mem == PP_MEM_HOST) {
+        PP_HIP_CHECK(hipMemcpyAsync(out, dout, out_e * 4, hipMemcpyDeviceToHost, s));
+        if (warp_u8) PP_HIP_CHECK(hipMemcpyAsync(warp_u8, dwarp, warp_b, hipMemcpyDeviceToHost, s));
+    }
+    // the staged transforms / table live in ctx scratch: finish before another call can reuse it
     PP_HIP_CHECK(hipStreamSynchronize(s));
     return PP_OK;
 }

@@ -85,6 +85,48 @@ class VideoInfo(dj.Computed):  # pipeline.py:92-102
 
 
 @schema
+class BottomUpMethodLookup(dj.Lookup):  # pipeline.py:133-147
+    definition = """
+    bottom_up_method_name : varchar(50)
+    """
+    contents = [
+        {"bottom_up_method_name": "OpenPose"},
+        {"bottom_up_method_name": "OpenPose_BODY25B"},
+        {"bottom_up_method_name": "OpenPose_HR"},
+        {"bottom_up_method_name": "OpenPose_LR"},
+        {"bottom_up_method_name": "MMPose"},
+        # this uses the COCO25 keypoints but in the same order as OpenPose
+        {"bottom_up_method_name": "Bridging_OpenPose"},
+    ]
+
+
+@schema
+class BottomUpMethod(dj.Manual):  # pipeline.py:150-155
+    definition = """
+    -> Video
+    -> BottomUpMethodLookup
+    """
+
+
+@schema
+class BottomUpPeople(dj.Computed):  # pipeline.py:158-165
+    definition = """
+    -> BottomUpMethod
+    ---
+    keypoints                   : longblob
+    timestamp=CURRENT_TIMESTAMP : timestamp    # automatic timestamp
+    """
+
+    def make(self, key):  # pipeline.py:167-245
+        if key["bottom_up_method_name"] == "MMPose":
+            from .wrappers.mmpose import mmpose_bottom_up
+            key["keypoints"] = mmpose_bottom_up(key)
+        else:          # the OpenPose / Bridging rows need third-party code that is not built
+            raise Exception("Method not implemented")
+        self.insert1(key)
+
+
+@schema
 class TrackingBboxMethodLookup(dj.Lookup):  # pipeline.py:480-494
     definition = """
     tracking_method      : int
@@ -232,6 +274,28 @@ class BestDetectedFrames(dj.Computed):  # pipeline.py:770-785
     @property
     def key_source(self):  # pipeline.py:783-785
         return Video & DetectedFrames
+
+
+@schema
+class BottomUpPerson(dj.Computed):  # pipeline.py:788-795
+    definition = """
+    -> PersonBbox
+    -> BottomUpPeople
+    ---
+    keypoints        : longblob
+    """
+
+    def make(self, key):  # pipeline.py:797-810
+        from .keypoint_matching import match_keypoints_to_bbox
+        print(key)
+        keypoints = (BottomUpPeople & key).fetch1("keypoints")
+        bbox = (PersonBbox & key).fetch1("bbox")
+        # num_keypoints=17: the reference leaves the default 25 (OpenPose), so an unmatched frame of a COCO track is a (25, 3)
+        # row among (17, 3) rows and `np.array` gives a ragged object array; 17 keeps the result rectangular (INTEGRATION.md)
+        res = [match_keypoints_to_bbox(bbox[idx], keypoints[idx], num_keypoints=17) for idx in range(bbox.shape[0])]
+        keypoints, _ = list(zip(*res))
+        key["keypoints"] = np.array(keypoints)
+        self.insert1(key)
 
 
 @schema

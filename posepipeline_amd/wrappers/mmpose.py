@@ -1,4 +1,4 @@
-"""Drop-in for pose_pipeline/wrappers/mmpose.py:26-81 `mmpose_top_down_person`.
+"""Drop-in for pose_pipeline/wrappers/mmpose.py:26-81 `mmpose_top_down_person` and :84-121 `mmpose_bottom_up`.
 
 Same signature, same table reads (`PersonBbox.bbox`, the video of `key`), same return value
 (ndarray (N, K, 3) = [x_px, y_px, score]; a frame whose bbox contains NaN yields zeros((K, 3)), which
@@ -134,3 +134,52 @@ def mmpose_top_down_person(key, method='HRNet_W48_COCO'):
     results = top_down_batches(td, num_keypoints, cap, bboxes)
     cap.release()
     return np.asarray(results)
+
+
+# ---- bottom-up (wrappers/mmpose.py:84-121) -----------------------------------------------------------------------------------
+_bottom_up_cache: dict = {}
+last_timing: dict = {}      # per-stage wall time (s) of the last mmpose_bottom_up call
+
+
+def _bottom_up_stage(device=0):
+    """BottomUpStage of the VENDORED model, built once per process.  The reference assigns higher_hrnet48_coco_512x512 and its
+    checkpoint (:91-92) and then overwrites both with a MobileNetV2 config at an absolute path in the author's home directory
+    (:94-95), which no other machine has: the vendored pair is what is built here."""
+    if device not in _bottom_up_cache:
+        from ..bottomup import BottomUpStage
+        _bottom_up_cache[device] = BottomUpStage(device=device)
+    return _bottom_up_cache[device]
+
+
+def mmpose_bottom_up(key):
+    """Same signature and table reads as the reference (the video of `key`).  Returns one float32 (P, 17, 3) array
+    [x_px, y_px, score] per frame, persons in descending score; a frame without a person yields (0, 17, 3) where the reference's
+    `np.stack` raises.  The frames are streamed to the device in chunks; each chunk and its mirrored copy go through ONE program
+    run, and the associative-embedding post-processing runs on the device (posepipeline_amd/bottomup.py).  The video file is
+    not deleted (Video.get_robust_reader hands out a path the caller owns)."""
+    import time
+
+    from ..bottomup import CHUNK
+    from ..pipeline import Video
+    from ..streaming import FrameStreamer
+
+    stage = _bottom_up_stage()
+    stage.last_timing = {}
+    t0 = time.perf_counter()
+    video = Video.get_robust_reader(key, return_cap=False)
+    cap = open_video(video)
+    n = int(cap.num_frames)
+    keypoints = []
+    if n:
+        streamer = FrameStreamer(stage.ctx, cap, min(CHUNK, n), max_frames=n)
+        try:
+            for dev_ptr, m, first in streamer:
+                keypoints.extend(stage.run(dev_ptr, frames_dev_shape=(m, streamer.h, streamer.w)))
+                streamer.release()
+        finally:
+            streamer.close()
+    cap.release()
+    assert len(keypoints) == n, "video ended before its announced length"        # reference :109 asserts every frame decodes
+    last_timing.clear()
+    last_timing.update(stage.last_timing, total=time.perf_counter() - t0, frames=n)
+    return keypoints
