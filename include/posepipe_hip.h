@@ -49,7 +49,8 @@ extern "C" {
                                  pp_net_input_amax is a one-shot promise; PP_OP_BILINEAR_ADD (an added op type over existing pp_op
                                  fields: no struct or signature changed, so the version stays 10);
                                  PP_OP_DWCONV3X3 / PP_OP_LAYERNORM / PP_OP_WINDOW_ATTN / PP_OP_GELU_ADD and PP_ACT_GELU (the HRFormer
-                                 blocks) were added the same way */
+                                 blocks) were added the same way, and so were PP_OP_ATTENTION and the pp_poseformer_* / pp_attention_f32
+                                 entry points (added functions only) */
 
 typedef enum {
     PP_OK = 0,
@@ -181,8 +182,18 @@ typedef enum {
                                   out_i = sum_j softmax_j(attn[i][j]) v_j.
                                 A padded token takes part as a key with k = b_k, v = b_v (mmpose pads BEFORE the qkv Linear, and
                                 0 . W + b = b exactly); its own output is cropped away.  Channels [cin, cout) of `out` are exact zeros */
-    PP_OP_GELU_ADD = 14      /* out = res1 + gelu(in) (res1 = -1: out = gelu(in)); in, res1, out [h][w][c], cin = cout = c % 4 == 0, out
+    PP_OP_GELU_ADD = 14,     /* out = res1 + gelu(in) (res1 = -1: out = gelu(in)); in, res1, out [h][w][c], cin = cout = c % 4 == 0, out
                                 distinct from in and res1.  The last GELU of CrossFFN and the block's residual add in one pass */
+    PP_OP_ATTENTION = 15     /* global multi-head self-attention in float32 (poseformer.hip; the temporal stage of PoseFormer), one sample =
+                                one sequence of h * w <= 128 tokens.  in [h][w][3 * cout] = the qkv map, a 1x1 PP_OP_CONV of the LayerNorm
+                                output: channel s * cout + head * hd + d holds (q, k, v)[s] of head `head`, s = 0, 1, 2, hd = cin / heads;
+                                channels [cin, cout) of each third are padding and are not read.  out [h][w][cout].  cin = c_real = heads * hd
+                                (hd % 4 == 0, hd <= 128), cout = the out buffer's channels (% 4 == 0), stride = heads (as PP_OP_WINDOW_ATTN);
+                                no parameters.  Per sample and head, over the tokens i, j:
+                                  out_i = sum_j softmax_j((q_i . k_j) * hd^-0.5) v_j,
+                                each dot product one fmaf chain over d, the row maximum subtracted before exp, the sum over j one fmaf
+                                chain in token order; no atomics.  Channels [cin, cout) of `out` are exact zeros.  Existing pp_op fields
+                                only: sizeof(pp_op) and PP_ABI_VERSION are unchanged */
 } pp_op_type;
 
 #define PP_RELU_NONE 0
@@ -697,6 +708,43 @@ int pp_bottomup_candidates(pp_ctx* ctx, const float* hm, const float* s0, int n_
 int pp_bottomup_refine(pp_ctx* ctx, const float* hm, const float* s0, int n_frames, int k, int h0, int w0,
                        const int32_t* flip_perm, int hr, int wr, int align_corners, int n_person,
                        const int32_t* person_frame, const float* mean_tag, const int32_t* need, float* out);
+
+/* ---- PoseFormer lifting (poseformer.hip; models/poseformer.py, wrappers/poseformer.py) ------------------------------------------
+ * The 81-frame PoseFormer (ICCV 2021) behind pose_pipeline/wrappers/poseformer.py `process_liftformer`: 17 joints, 32 channels per
+ * joint, 8 heads, 4 + 4 blocks, mlp ratio 2; inference mode.  An UNPINNED restatement of common/model_poseformer.py.
+ *
+ * pp_attention_f32: PP_OP_ATTENTION on its own.  qkv [batch][tokens][3 * c_buf] and out [batch][tokens][c_buf] are DEVICE pointers,
+ * 16-byte aligned; c_real = heads * head dim real channels per third.  Queued on the context's stream, not synchronised.
+ *
+ * pp_poseformer_spatial: the spatial transformer, ONE launch for n_frames frames: kpts2d_norm [n_frames][17][2] (kpts_mem: host or
+ * device) -> features [n_frames][544] (DEVICE), index joint * 32 + channel.  params: DEVICE pointer, 16-byte aligned, to
+ * pp_poseformer_spatial_param_floats() floats in torch layouts:
+ *   Spatial_patch_to_embedding.weight [32][2], .bias [32], Spatial_pos_embed [17][32],
+ *   4 x { norm1.weight, norm1.bias, attn.qkv.weight [96][32], attn.qkv.bias [96], attn.proj.weight [32][32], attn.proj.bias,
+ *         norm2.weight, norm2.bias, mlp.fc1.weight [64][32], mlp.fc1.bias [64], mlp.fc2.weight [32][64], mlp.fc2.bias },
+ *   Spatial_norm.weight, Spatial_norm.bias.
+ * A frame's features depend on that frame and the parameters only: not on n_frames, not on the frame's position.  With a host input
+ * the call returns after one stream synchronisation, with a device input it only queues.
+ *
+ * pp_poseformer_lift: the whole lifter.  `net` is the temporal program (models/poseformer.py): in_buf [1][81][c], out_buf [1][81][c]
+ * = Temporal_norm's output, c >= 544 with channels >= 544 exact zeros.  spatial_off / pos_off / head_off: float offsets (multiples
+ * of 4) into the net's weight blob of the spatial parameter block above, of Temporal_pos_embed [81][544], and of the head block of
+ * pp_poseformer_head_param_floats() floats: weighted_mean.weight [81] padded to 84, weighted_mean.bias padded to 4, head.0.weight
+ * [544], head.0.bias [544], head.1.weight [51][544], head.1.bias [51] padded to 52.
+ *   kpts2d_norm [n_frames][17][2], n_frames >= 81 -> out [n_frames - 80][51]: row i is the window [i, i + 81), i.e. frame i + 40.
+ * The spatial kernel runs once over the clip; the windows then go, in batches of the net's max_batch, through
+ *   win[b][f][:] = features[i_b + f][:] + pos[f][:]  ->  the program  ->  y[c] = sum_f w[f] x[f][c] + b, LayerNorm(eps 1e-5), Linear.
+ * What a window's sample holds does not depend on the batch it shares.  mem: where kpts2d_norm and out live (PP_MEM_HOST: one upload,
+ * one download).  Everything is queued on the context's stream and the call returns after ONE stream synchronisation.
+ * stage_ms (optional, host float[4]): device milliseconds of this call by HIP events, summed over the batches: spatial kernel,
+ * gather, temporal program, mean + head.
+ */
+int pp_attention_f32(pp_ctx* ctx, const float* qkv, int batch, int tokens, int heads, int c_real, int c_buf, float* out);
+int pp_poseformer_spatial_param_floats(void);
+int pp_poseformer_head_param_floats(void);
+int pp_poseformer_spatial(pp_ctx* ctx, const float* params, const float* kpts2d_norm, int n_frames, int kpts_mem, float* features);
+int pp_poseformer_lift(pp_net* net, int in_buf, int out_buf, long long spatial_off, long long pos_off, long long head_off,
+                       const float* kpts2d_norm, int n_frames, float* out, int mem, float* stage_ms);
 
 #ifdef __cplusplus
 }

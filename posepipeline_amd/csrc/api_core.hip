@@ -593,6 +593,16 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
         PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0, "op %d: window_attn has no residuals or slices", idx);
         PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)169 * op.stride <= net.n_weights && op.b_off >= 0 &&
                        (op.b_off % 4) == 0 && (size_t)op.b_off + (size_t)3 * op.cout <= net.n_weights, "op %d: window_attn parameters out of blob", idx);
+    } else if (op.type == PP_OP_ATTENTION) {
+        PP_REQUIRE(op.stride > 0 && op.cin > 0 && op.cin % op.stride == 0 && op.cin <= op.cout && (op.cout & 3) == 0 &&
+                       ((op.cin / op.stride) & 3) == 0 && op.cin / op.stride <= pp_attention_f32_max_head_dim(),
+                   "op %d: attention needs cin = heads (stride) * head dim (a multiple of 4, at most %d) <= cout, cout %% 4 == 0", idx,
+                   pp_attention_f32_max_head_dim());
+        PP_REQUIRE(bi.c == 3 * op.cout && bo.c == op.cout && bi.h == bo.h && bi.w == bo.w && op.in != op.out &&
+                       (long long)bi.h * bi.w <= pp_attention_f32_max_tokens(),
+                   "op %d: attention needs in [h][w][3 * cout] (the qkv map) and out [h][w][cout], h * w <= %d tokens", idx,
+                   pp_attention_f32_max_tokens());
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0, "op %d: attention has no residuals or slices", idx);
     } else if (op.type == PP_OP_GELU_ADD) {
         PP_REQUIRE(op.cin == op.cout && op.cout > 0 && (op.cout & 3) == 0 && bi.c == op.cout && bo.c == op.cout && bi.h == bo.h &&
                        bi.w == bo.w && op.in != op.out, "op %d: gelu_add needs distinct in / out buffers [h][w][c], c %% 4 == 0", idx);
@@ -706,6 +716,8 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
     } else if (op.type == PP_OP_WINDOW_ATTN) {
         return pp_launch_window_attn(net->buf_ptr(op.in), net->weights + op.w_off, net->weights + op.b_off, net->buf_ptr(op.out), batch,
                                      bi.h, bi.w, op.cin, op.cout, op.stride, s);
+    } else if (op.type == PP_OP_ATTENTION) {
+        return pp_launch_attention_f32(net->buf_ptr(op.in), net->buf_ptr(op.out), batch, bi.h * bi.w, op.stride, op.cin, op.cout, s);
     } else if (op.type == PP_OP_GELU_ADD) {
         return pp_launch_gelu_add(net->buf_ptr(op.in), op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr, net->buf_ptr(op.out),
                                   (size_t)batch * net->buf_elems[op.in], s);
@@ -723,6 +735,11 @@ int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c) {
 }
 int pp_net_max_batch(pp_net* net) { return net ? net->max_batch : 0; }
 pp_ctx* pp_net_ctx(pp_net* net) { return net ? net->ctx : nullptr; }
+// the resident weight blob (device pointer) and its length in floats
+const float* pp_net_weights(pp_net* net, size_t* n_weights) {
+    if (n_weights) *n_weights = net ? net->n_weights : 0;
+    return net ? net->weights : nullptr;
+}
 
 // the caller's own kernel has just overwritten `buf`: a pending promise of its maxima (pp_net_input_amax) is void
 void pp_net_void_input_amax(pp_net* net, int buf) {

@@ -253,6 +253,10 @@ int pp_launch_gelu_add(const float* x, const float* res, float* y, size_t elems,
 int pp_launch_window_attn(const float* qkv, const float* table, const float* bias, float* out, int n, int h, int w, int c_real,
                           int c_buf, int heads, hipStream_t stream);
 int pp_window_attn_max_head_dim();
+// ---- PP_OP_ATTENTION (poseformer.hip): global multi-head self-attention, float32; qkv [batch][tokens][3 * c_buf] -> out [batch][tokens][c_buf]
+int pp_launch_attention_f32(const float* qkv, float* out, int batch, int tokens, int heads, int c_real, int c_buf, hipStream_t stream);
+int pp_attention_f32_max_tokens();
+int pp_attention_f32_max_head_dim();
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

@@ -69,6 +69,7 @@ class Program:
     flops: float = 0.0              # algorithmic FLOPs per sample (2 * MACs of the real, unpadded convs)
     op_flops: list = field(default_factory=list)
     op_names: list = field(default_factory=list)
+    param_offsets: dict = field(default_factory=dict)   # name -> float offset into blob of a parameter block no op points at (add_params)
 
 
 class ProgramBuilder:
@@ -78,6 +79,7 @@ class ProgramBuilder:
         self.blob_parts: list[np.ndarray] = []
         self.blob_len = 0
         self.named: dict[str, int] = {}
+        self.param_offsets: dict[str, int] = {}
 
     # ---- buffers -----------------------------------------------------------------------------
     def buf(self, h, w, c, name=None, pinned=False) -> int:
@@ -90,6 +92,19 @@ class ProgramBuilder:
     def dims(self, vid):
         b = self.vbufs[vid]
         return b.h, b.w, b.c
+
+    def mark_output(self, vid, name) -> int:
+        """name an existing buffer (an op's result): it keeps a physical buffer of its own, which callers find under Program.named"""
+        self.vbufs[vid].pinned = True
+        self.named[name] = vid
+        return vid
+
+    def add_params(self, name, arr) -> int:
+        """a parameter block that rides in the weight blob without an op pointing at it (kernels outside the program read it from the
+        net's resident blob); its float offset, a multiple of 4, is returned and kept in Program.param_offsets[name]"""
+        assert name not in self.param_offsets, name
+        self.param_offsets[name] = self._add_blob(arr)
+        return self.param_offsets[name]
 
     def _add_blob(self, arr) -> int:
         arr = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
@@ -297,6 +312,19 @@ class ProgramBuilder:
                               flops=2.0 * n_win * 2 * t * t * c_real))
         return out
 
+    def attention(self, qkv, *, c_real, heads, name="attention") -> int:
+        """Global float32 multi-head self-attention (PP_OP_ATTENTION) on a qkv map [h][w][3 * c_buf] (channel s * c_buf + head * hd + d;
+        a 1x1 convolution of the LayerNorm output writes it); one sample is one sequence of h * w <= 128 tokens.  Returns
+        [h][w][c_buf] with channels >= c_real exact zeros."""
+        h, w, c3 = self.dims(qkv)
+        c_buf = c3 // 3
+        assert c3 == 3 * c_buf and c_buf % 4 == 0 and c_real <= c_buf and c_real % heads == 0, (c3, c_real, heads)
+        hd = c_real // heads
+        assert hd % 4 == 0 and hd <= 128 and h * w <= 128, (hd, h, w)
+        out = self.buf(h, w, c_buf)
+        t = h * w
+        return self._plain_op(L.PP_OP_ATTENTION, qkv, out, cin=c_real, cout=c_buf, stride=heads, name=name, flops=2.0 * 2 * t * t * c_real)
+
     def gelu_add(self, x, *, res1=-1, name="gelu_add") -> int:
         """out = res1 + gelu(x)  (res1 = -1: gelu(x))"""
         h, w, c = self.dims(x)
@@ -449,7 +477,8 @@ class ProgramBuilder:
         named = {k: v2p[v] for k, v in self.named.items()}
         return Program(ops=ops, bufs=phys_dims, buf_pad=phys_pad, blob=blob, named=named,
                        flops=float(sum(op["flops"] for op in self.vops)),
-                       op_flops=[op["flops"] for op in self.vops], op_names=[op["name"] for op in self.vops])
+                       op_flops=[op["flops"] for op in self.vops], op_names=[op["name"] for op in self.vops],
+                       param_offsets=dict(self.param_offsets))
 
 
 class Net:

@@ -31,10 +31,18 @@ def load_state_dict(path: str, key_candidates=("state_dict", "model_pos")) -> di
     return {k: v.detach().cpu().numpy() for k, v in sd.items() if hasattr(v, "detach")}
 
 
-def get_state_dict(relpath: str, shapes: dict, seed: int, synth=None) -> dict:
+def strip_key_prefix(sd: dict, prefix: str) -> dict:
+    """`prefix` dropped from the front of every key that has it (`module.` of a checkpoint saved from an nn.DataParallel model)"""
+    return {(k[len(prefix):] if k.startswith(prefix) else k): v for k, v in sd.items()}
+
+
+def get_state_dict(relpath: str, shapes: dict, seed: int, synth=None, strip_prefix=None) -> dict:
+    """strip_prefix: dropped from the front of every checkpoint key that has it (`module.` of an nn.DataParallel checkpoint)"""
     path = os.path.join(model_data_dir(), relpath)
     if os.path.exists(path):
         sd = load_state_dict(path)
+        if strip_prefix:
+            sd = strip_key_prefix(sd, strip_prefix)
         missing = [k for k in shapes if k not in sd]
         if missing:
             raise KeyError(f"{path}: missing parameters {missing[:5]}{'...' if len(missing) > 5 else ''}")
