@@ -194,6 +194,8 @@ typedef enum {
                                 each dot product one fmaf chain over d, the row maximum subtracted before exp, the sum over j one fmaf
                                 chain in token order; no atomics.  Channels [cin, cout) of `out` are exact zeros.  Existing pp_op fields
                                 only: sizeof(pp_op) and PP_ABI_VERSION are unchanged */
+    /* PP_OP_DCN3X3 = 16 and PP_OP_DWDECONV = 17 (the DCN up-sampling head of DLA-34, fairmot.hip) are #defined at the end of this
+     * header, with the FairMOT entry points: the header grows only at its end */
 } pp_op_type;
 
 #define PP_RELU_NONE 0
@@ -745,6 +747,56 @@ int pp_poseformer_head_param_floats(void);
 int pp_poseformer_spatial(pp_ctx* ctx, const float* params, const float* kpts2d_norm, int n_frames, int kpts_mem, float* features);
 int pp_poseformer_lift(pp_net* net, int in_buf, int out_buf, long long spatial_off, long long pos_off, long long head_off,
                        const float* kpts2d_norm, int n_frames, float* out, int mem, float* stage_ms);
+
+/* ---- FairMOT (fairmot.hip; models/dla.py, wrappers/fairmot.py) -------------------------------------------------------------------
+ * The one-shot tracker behind pose_pipeline/wrappers/fairmot.py `fairmot_bounding_boxes`: DLA-34 with the DCN up-sampling head
+ * (pose_dla_dcn), heads hm 1 / wh 4 / id 128 / reg 2.  FairMOT, DCNv2 and OpenCV are not vendored: UNPINNED restatements
+ * (INTEGRATION.md); numpy twins in tests/fairmot_ref.py.  Two op types, added over existing pp_op fields: sizeof(pp_op) and
+ * PP_ABI_VERSION are unchanged.
+ *
+ * PP_OP_DCN3X3: modulated deformable 3x3 convolution (DCNv2; stride 1, padding 1, dilation 1, one deformable group).
+ *   in  [h][w][cin] (cin % 4 == 0);  in2 [h][w][>= 27] the offset / mask tensor, written by an ordinary PP_OP_CONV (conv_offset_mask):
+ *   channel 2k = dy and 2k + 1 = dx of tap k = 3 i + j, channel 18 + k = the mask LOGIT of tap k (sigmoid applied here, evaluated in
+ *   double and rounded once);  out [h][w][cout], cout <= 256.  kh = kw = 3, stride = 1, pad_h = pad_w = 1.
+ *   w_off: W[9][cin_p][cout_p] (tap major; cin_p, cout_p = cin, cout rounded up to 32, zero filled), b_off: bias[cout_p].
+ *   Sample position of tap k at output (y, x): py = float(y - 1 + i) + dy, px = float(x - 1 + j) + dx (float32).  The sample is 0
+ *   unless -1 < py < h and -1 < px < w; else with y0 = floor(py), x0 = floor(px), lh = py - y0, lw = px - x0, hh = 1 - lh, hw = 1 - lw:
+ *     sample[ci] = (((hh hw) v00 + (hh lw) v01) + (lh hw) v10) + (lh lw) v11,   v.. = x[y0 + .][x0 + .][ci], 0 outside the map
+ *   (DCNv2's dmcn_im2col_bilinear), each product and sum rounded to float32, then column = sample * mask.
+ *   out[y][x][co] = act(sum_k sum_ci W[k][ci][co] column_k[ci] + bias[co]): ONE fmaf chain over (k, ci) in that order from 0 (the
+ *   float32-input MFMA), then + bias; relu: PP_RELU_NONE / PP_RELU_LAST.  The same kernel in exact and split nets.
+ *   The columns of a tile of 64 output pixels exist in LDS only; no column tensor is written to global memory.
+ * PP_OP_DWDECONV: depthwise ConvTranspose2d(c, c, 2 s, stride s, padding s / 2, groups = c, bias = False), s = stride even.
+ *   in [h][w][c] -> out [h s][w s][c], cin = cout = c % 4 == 0, kh = kw = 2 s, pad_h = pad_w = s / 2; w_off: w[2 s][2 s][c].
+ *   out[oy][ox][c] = sum over (ky ascending, kx ascending) with (oy + pad - ky) = s iy, (ox + pad - kx) = s ix inside the map of
+ *   in[iy][ix][c] * w[ky][kx][c]: acc = 0, acc = acc + x * w, each rounded to float32 (no FMA); at most 2 x 2 terms.
+ *   res1 >= 0: out = acc + res1[oy][ox][c] (one more float32 add: bit-identical to a separate addition).
+ */
+#define PP_OP_DCN3X3 16
+#define PP_OP_DWDECONV 17
+/* pp_fairmot_input_size: network size (hp, wp) = (608, 1088), or (1088, 608) when src_h > src_w; every frame is first resized to
+ * 1920 x 1080 whatever its size (upstream LoadVideo), then letterboxed: ratio = min(hp / 1080, wp / 1920), (nw, nh) =
+ * (round(1920 ratio), round(1080 ratio)), top = round((hp - nh) / 2 - 0.1), left = round((wp - nw) / 2 - 0.1), Python's round.
+ *
+ * pp_fairmot_preprocess: frames [n][src_h][src_w][3] u8 BGR (frames_mem: host or device) -> out_device [n][hp][wp][4] float32 =
+ * (R, G, B, 0) / 255.  Per output pixel inside the letterbox: cv2.resize(INTER_AREA) from the 1920 x 1080 image (float32 tables
+ * of computeResizeAreaTab; buf = sum_k S[sx_k] alpha_k from 0 in k order, sum = beta_0 buf_0, sum = sum + beta_j buf_j; stored with
+ * round half to even, clamped to [0, 255]), whose pixels are the source's (1920 x 1080 sources) or cv2.resize(INTER_LINEAR)'s 8-bit
+ * fixed-point bilinear (11-bit coefficients, (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2), recomputed where needed.
+ * Outside: 128 / 255.  Returns after one stream synchronisation.
+ *
+ * pp_fairmot_decode: head maps, DEVICE pointers, NHWC: hm [n][h][w][1] logits, wh [n][h][w][4], reg [n][h][w][2], id [n][h][w][id_dim].
+ *   score = float32 sigmoid (evaluated in double, rounded once); a pixel is a peak when no pixel of its 3x3 neighbourhood (clipped
+ *   to the map) has a larger score -- a plateau keeps all its members.  The K (<= h w) largest peaks in descending order; EQUAL
+ *   SCORES RANK BY THE LOWER FLAT INDEX y w + x (torch.topk leaves that order unspecified).
+ *   dets [n][K][5] = (xs - wh0, ys - wh1, xs + wh2, ys + wh3, score), xs = x + reg0, ys = y + reg1, in heat-map cells;
+ *   feats [n][K][id_dim] = id / max(||id||_2, 1e-12); inds [n][K] the flat indices.  Slots beyond the number of peaks hold index -1
+ *   and zeros.  mem: where dets / feats / inds live (PP_MEM_HOST: copied back, one stream synchronisation). */
+int pp_fairmot_input_size(int src_h, int src_w, int32_t* hp, int32_t* wp, int32_t* nh, int32_t* nw, int32_t* top, int32_t* left);
+int pp_fairmot_preprocess(pp_ctx* ctx, const uint8_t* frames, int n, int src_h, int src_w, int frames_mem, int hp, int wp, int nh,
+                          int nw, int top, int left, float* out_device);
+int pp_fairmot_decode(pp_ctx* ctx, const float* hm, const float* wh, const float* reg, const float* id, int n, int h, int w, int K,
+                      int id_dim, float* dets, float* feats, int32_t* inds, int mem);
 
 #ifdef __cplusplus
 }

@@ -470,8 +470,9 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
     const int nb = (int)net.bufs.size();
     PP_REQUIRE(op.in >= 0 && op.in < nb && op.out >= 0 && op.out < nb, "op %d: buffer id out of range", idx);
     PP_REQUIRE(op.res1 < nb && op.res2 < nb, "op %d: residual buffer id out of range", idx);
-    PP_REQUIRE(op.in2 < nb && op.in3 < nb && (op.type == PP_OP_UPSAMPLE_ADD || op.type == PP_OP_BILINEAR_ADD || (op.in2 < 0 && op.in3 < 0)),
-               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD / PP_OP_BILINEAR_ADD only (-1 elsewhere)", idx);
+    PP_REQUIRE(op.in2 < nb && op.in3 < nb && (op.type == PP_OP_UPSAMPLE_ADD || op.type == PP_OP_BILINEAR_ADD ||
+                                              (op.type == PP_OP_DCN3X3 && op.in3 < 0) || (op.in2 < 0 && op.in3 < 0)),
+               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD / PP_OP_BILINEAR_ADD (in2: PP_OP_DCN3X3) only (-1 elsewhere)", idx);
     const pp_buf& bi = net.bufs[op.in];
     const pp_buf& bo = net.bufs[op.out];
     const int eh = op.pad_end & 1, ew = (op.pad_end >> 1) & 1;   // TensorFlow SAME: the odd padding row / column goes last
@@ -610,6 +611,31 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
         if (op.res1 >= 0)
             PP_REQUIRE(net.bufs[op.res1].c == bo.c && net.bufs[op.res1].h == bo.h && net.bufs[op.res1].w == bo.w && op.res1 != op.out,
                        "op %d: gelu_add res1 must be a [h][w][c] buffer other than out", idx);
+    } else if (op.type == PP_OP_DCN3X3) {
+        PP_REQUIRE(op.in2 >= 0 && op.in2 != op.out && op.in != op.out, "op %d: dcn3x3 needs the offset / mask buffer in in2 and a distinct out buffer", idx);
+        const pp_buf& bm = net.bufs[op.in2];
+        PP_REQUIRE(op.cin > 0 && (op.cin & 3) == 0 && bi.c == op.cin && op.cout > 0 && op.cout <= pp_dcn3x3_max_cout() && bo.c == op.cout &&
+                       bo.h == bi.h && bo.w == bi.w && bm.h == bi.h && bm.w == bi.w && bm.c >= 27,
+                   "op %d: dcn3x3 needs in [h][w][cin %% 4 == 0], in2 [h][w][>= 27] and out [h][w][cout <= %d]", idx, pp_dcn3x3_max_cout());
+        PP_REQUIRE(op.kh == 3 && op.kw == 3 && op.stride == 1 && op.pad_h == 1 && op.pad_w == 1 && op.dil_h == 1 && op.dil_w == 1,
+                   "op %d: dcn3x3 is 3x3, stride 1, padding 1, dilation 1", idx);
+        PP_REQUIRE(op.relu == PP_RELU_NONE || op.relu == PP_RELU_LAST, "op %d: dcn3x3 supports PP_RELU_NONE / PP_RELU_LAST", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.out_c_off == 0 && op.up_log2 == 0, "op %d: dcn3x3 has no residuals, slices or upsampling", idx);
+        const size_t cin_p = ((size_t)op.cin + 31) / 32 * 32, cout_p = ((size_t)op.cout + 31) / 32 * 32;
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + 9 * cin_p * cout_p <= net.n_weights && op.b_off >= 0 &&
+                       (op.b_off % 4) == 0 && (size_t)op.b_off + cout_p <= net.n_weights, "op %d: dcn3x3 parameters out of blob", idx);
+    } else if (op.type == PP_OP_DWDECONV) {
+        PP_REQUIRE(op.cin == op.cout && op.cout > 0 && (op.cout & 3) == 0 && bi.c == op.cout && bo.c == op.cout && op.in != op.out &&
+                       op.stride >= 2 && (op.stride & 1) == 0 && op.kh == 2 * op.stride && op.kw == 2 * op.stride &&
+                       op.pad_h == op.stride / 2 && op.pad_w == op.stride / 2 && bo.h == bi.h * op.stride && bo.w == bi.w * op.stride,
+                   "op %d: dwdeconv needs in [h][w][c] and out [h s][w s][c], c %% 4 == 0, kernel 2 s, padding s / 2, s even", idx);
+        PP_REQUIRE(op.res2 < 0 && !op.out_nchw && op.out_c_off == 0 && op.up_log2 == 0 && op.relu == PP_RELU_NONE,
+                   "op %d: dwdeconv has no res2, slices, upsampling or activation", idx);
+        if (op.res1 >= 0)
+            PP_REQUIRE(net.bufs[op.res1].c == bo.c && net.bufs[op.res1].h == bo.h && net.bufs[op.res1].w == bo.w && op.res1 != op.out,
+                       "op %d: dwdeconv res1 must be a [h s][w s][c] buffer other than out", idx);
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)op.kh * op.kw * op.cout <= net.n_weights,
+                   "op %d: dwdeconv parameters out of blob", idx);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         PP_REQUIRE(op.cin == op.cout && bi.c == op.cin && bo.c == op.cin && bi.h == bo.h && bi.w == bo.w && op.in != op.out,
                    "op %d: vit encoder needs distinct in / out buffers of [h][w][dim]", idx);
@@ -721,6 +747,12 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
     } else if (op.type == PP_OP_GELU_ADD) {
         return pp_launch_gelu_add(net->buf_ptr(op.in), op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr, net->buf_ptr(op.out),
                                   (size_t)batch * net->buf_elems[op.in], s);
+    } else if (op.type == PP_OP_DCN3X3) {
+        return pp_launch_dcn3x3(net->buf_ptr(op.in), net->buf_ptr(op.in2), net->weights + op.w_off, net->weights + op.b_off,
+                                net->buf_ptr(op.out), batch, bi.h, bi.w, op.cin, op.cout, net->bufs[op.in2].c, op.relu == PP_RELU_LAST, s);
+    } else if (op.type == PP_OP_DWDECONV) {
+        return pp_launch_dwdeconv(net->buf_ptr(op.in), net->weights + op.w_off, op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr,
+                                  net->buf_ptr(op.out), batch, bi.h, bi.w, op.cout, op.stride, s);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         pp_vit_encoder* enc = net->vits[&op - net->ops.data()];
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);

@@ -257,6 +257,14 @@ int pp_window_attn_max_head_dim();
 int pp_launch_attention_f32(const float* qkv, float* out, int batch, int tokens, int heads, int c_real, int c_buf, hipStream_t stream);
 int pp_attention_f32_max_tokens();
 int pp_attention_f32_max_head_dim();
+// ---- PP_OP_DCN3X3 / PP_OP_DWDECONV (fairmot.hip; field by field in posepipe_hip.h) ---------------------------------------------
+// x [n][h][w][cin], om [n][h][w][om_c >= 27], wgt [9][cin_p32][cout_p32], bias [cout_p32] -> y [n][h][w][cout]
+int pp_launch_dcn3x3(const float* x, const float* om, const float* wgt, const float* bias, float* y, int n, int h, int w, int cin,
+                     int cout, int om_c, int relu, hipStream_t stream);
+int pp_dcn3x3_max_cout();
+// x [n][h][w][c], wgt [2 s][2 s][c], res (may be null) and y [n][h s][w s][c]
+int pp_launch_dwdeconv(const float* x, const float* wgt, const float* res, float* y, int n, int h, int w, int c, int stride,
+                       hipStream_t stream);
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

@@ -164,3 +164,38 @@ def ecc_euclidean(ctx: L.Context, gray_dev: int, n_images: int, h: int, w: int, 
     L.check(ctx.lib.pp_ecc_euclidean(ctx.handle, C.c_void_p(gray_dev), n_images, h, w, L.ptr(pairs), k, int(num_iters), float(stop_eps),
                                      L.ptr(warp), L.ptr(rho), L.ptr(iters), L.ptr(status)), "pp_ecc_euclidean")
     return warp, rho, iters, status
+
+
+def fairmot_input_size(src_h: int, src_w: int):
+    """-> (hp, wp, nh, nw, top, left): FairMOT's network size for a source of this orientation and the letterbox of the 1920 x 1080
+    image every frame is resized to first (pp_fairmot_input_size)"""
+    v = [C.c_int32() for _ in range(6)]
+    L.check(L.load_library().pp_fairmot_input_size(int(src_h), int(src_w), *[C.byref(x) for x in v]), "pp_fairmot_input_size")
+    return tuple(int(x.value) for x in v)
+
+
+def fairmot_preprocess(ctx: L.Context, frames, out_dev: int, frames_dev_shape=None):
+    """frames: numpy [n][h][w][3] u8 BGR, or a device pointer (int) with frames_dev_shape = (n, h, w) -> device [n][hp][wp][4]
+    float32 RGB / 255 at out_dev (pp_fairmot_preprocess).  Returns the geometry of fairmot_input_size."""
+    if isinstance(frames, np.ndarray):
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, _ = frames.shape
+        mem = L.PP_MEM_HOST
+    else:
+        n, h, w = frames_dev_shape
+        mem = L.PP_MEM_DEVICE
+    geo = fairmot_input_size(h, w)
+    hp, wp, nh, nw, top, left = geo
+    L.check(ctx.lib.pp_fairmot_preprocess(ctx.handle, L.ptr(frames), n, h, w, mem, hp, wp, nh, nw, top, left, C.c_void_p(out_dev)),
+            "pp_fairmot_preprocess")
+    return geo
+
+
+def fairmot_decode(ctx: L.Context, hm_dev: int, wh_dev: int, reg_dev: int, id_dev: int, n: int, h: int, w: int, K: int, id_dim: int = 128):
+    """pp_fairmot_decode on device head maps (NHWC) -> (dets [n][K][5] float32, feats [n][K][id_dim] float32, inds [n][K] int32)"""
+    dets = np.zeros((n, K, 5), np.float32)
+    feats = np.zeros((n, K, id_dim), np.float32)
+    inds = np.zeros((n, K), np.int32)
+    L.check(ctx.lib.pp_fairmot_decode(ctx.handle, C.c_void_p(hm_dev), C.c_void_p(wh_dev), C.c_void_p(reg_dev), C.c_void_p(id_dev), n, h, w,
+                                      K, id_dim, L.ptr(dets), L.ptr(feats), L.ptr(inds), L.PP_MEM_HOST), "pp_fairmot_decode")
+    return dets, feats, inds

@@ -181,6 +181,9 @@ class TrackingBbox(dj.Computed):  # pipeline.py:508-513
         elif name == "MMTrack_qdtrack":
             from .wrappers.mmtrack import mmtrack_bounding_boxes
             tracks = mmtrack_bounding_boxes(video, "qdtrack")
+        elif name == "FairMOT":            # pipeline.py:549-553
+            from .wrappers.fairmot import fairmot_bounding_boxes
+            tracks = fairmot_bounding_boxes(video)
         else:
             raise Exception(f"Unsupported tracking method: {key['tracking_method']}")
         key["tracks"] = tracks

@@ -335,6 +335,51 @@ class ProgramBuilder:
                               in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, flops=0.0))
         return out
 
+    # ---- DLA-34's DCN up-sampling head (PP_OP_DCN3X3 / PP_OP_DWDECONV; include/posepipe_hip.h) ----------------------------------
+    def dcn3x3(self, x, offset_mask, weight, bias, *, relu=L.PP_RELU_NONE, name="dcn3x3") -> int:
+        """Modulated deformable 3x3 convolution (DCNv2, stride 1, padding 1, one deformable group).  offset_mask: the [h][w][>= 27]
+        buffer an ordinary conv (conv_offset_mask) wrote: 18 offsets (dy, dx per tap), then 9 mask logits.  weight: torch layout
+        [cout][cin][3][3] (BN already folded), bias [cout] or None."""
+        h, w, cin_buf = self.dims(x)
+        wt = np.asarray(weight, dtype=np.float32)
+        cout, cin = wt.shape[:2]
+        assert wt.shape == (cout, cin, 3, 3) and cin <= cin_buf and cin_buf % 4 == 0 and cout <= 256, (wt.shape, cin_buf)
+        oh, ow, oc = self.dims(offset_mask)
+        assert (oh, ow) == (h, w) and oc >= 27, (self.dims(offset_mask), h, w)
+        cin_p, cout_p = (cin_buf + 31) // 32 * 32, (cout + 31) // 32 * 32
+        wk = np.zeros((9, cin_p, cout_p), np.float32)                      # [tap][cin][cout]
+        wk[:, :cin, :cout] = np.transpose(wt.reshape(cout, cin, 9), (2, 1, 0))
+        bk = np.zeros(cout_p, np.float32)
+        if bias is not None:
+            bk[:cout] = np.asarray(bias, np.float32)
+        out = self.buf(h, w, cout)
+        w_off = self._add_blob(wk)
+        b_off = self._add_blob(bk)
+        self.vops.append(dict(type=L.PP_OP_DCN3X3, in_=x, out=out, res1=-1, res2=-1, cin=cin_buf, cout=cout, kh=3, kw=3, stride=1,
+                              pad_h=1, pad_w=1, dil_h=1, dil_w=1, relu=relu, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
+                              out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, in2=offset_mask, in3=-1,
+                              up2_log2=0, up3_log2=0, flops=2.0 * 9 * cin * cout * h * w))
+        return out
+
+    def dwdeconv(self, x, weight, stride, *, res1=-1, name="dwdeconv") -> int:
+        """Depthwise ConvTranspose2d(c, c, 2 * stride, stride, padding stride // 2, groups=c, bias=False).  weight: torch layout
+        [c][1][2s][2s].  res1: a [h s][w s][c] buffer added to the result (bit-identical to a separate addition)."""
+        h, w, c_buf = self.dims(x)
+        wt = np.asarray(weight, dtype=np.float32)
+        c, k = wt.shape[0], 2 * stride
+        assert wt.shape == (c, 1, k, k) and c <= c_buf and c_buf % 4 == 0 and stride >= 2 and stride % 2 == 0, (wt.shape, c_buf, stride)
+        wk = np.zeros((k, k, c_buf), np.float32)
+        wk[:, :, :c] = np.transpose(wt[:, 0], (1, 2, 0))
+        out = self.buf(h * stride, w * stride, c_buf)
+        if res1 >= 0:
+            assert self.dims(res1) == self.dims(out), (self.dims(res1), self.dims(out))
+        w_off = self._add_blob(wk)
+        self.vops.append(dict(type=L.PP_OP_DWDECONV, in_=x, out=out, res1=res1, res2=-1, cin=c_buf, cout=c_buf, kh=k, kw=k,
+                              stride=stride, pad_h=stride // 2, pad_w=stride // 2, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
+                              res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=0, name=name,
+                              flops=2.0 * 4 * c * h * w * stride * stride))
+        return out
+
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
         a 4-term gather (PP_OP_DECONV_BF16).  weight: torch ConvTranspose2d layout [cin][cout][4][4], BN already folded."""

@@ -510,3 +510,245 @@ class TracktorTracker:
         if len(ids) == 0:
             return np.zeros((0, 6), np.float32)
         return np.concatenate([ids[:, None].astype(np.float32), boxes, scores[:, None]], axis=1).astype(np.float32)
+
+
+# ---- FairMOT JDETracker (wrappers/fairmot.py) -------------------------------------------------------------------------------------
+class _STrack:
+    """one track of JDETracker (upstream STrack): state 0 New, 1 Tracked, 2 Lost, 3 Removed"""
+    __slots__ = ("tlwh0", "score", "mean", "cov", "is_activated", "state", "track_id", "frame_id", "start_frame", "tracklet_len",
+                 "curr_feat", "smooth_feat")
+
+    def __init__(self, tlwh, score, feat):
+        self.tlwh0 = np.asarray(tlwh, np.float64)
+        self.score = float(score)
+        self.mean = self.cov = None
+        self.is_activated = False
+        self.state, self.track_id, self.frame_id, self.start_frame, self.tracklet_len = 0, 0, 0, 0, 0
+        self.smooth_feat = None
+        self.update_features(feat)
+
+    def update_features(self, feat, alpha=0.9):
+        feat = np.asarray(feat, np.float64)
+        feat = feat / np.linalg.norm(feat)
+        self.curr_feat = feat
+        if self.smooth_feat is None:
+            self.smooth_feat = feat
+        else:
+            self.smooth_feat = alpha * self.smooth_feat + (1 - alpha) * feat
+        self.smooth_feat = self.smooth_feat / np.linalg.norm(self.smooth_feat)
+
+    @property
+    def tlwh(self):
+        if self.mean is None:
+            return self.tlwh0.copy()
+        ret = self.mean[:4].copy()
+        ret[2] *= ret[3]
+        ret[:2] -= ret[2:] / 2
+        return ret
+
+    @property
+    def tlbr(self):
+        ret = self.tlwh
+        ret[2:] += ret[:2]
+        return ret
+
+    def xyah(self):
+        ret = self.tlwh
+        ret[:2] += ret[2:] / 2
+        ret[2] /= ret[3]
+        return np.ascontiguousarray(ret)
+
+
+def jde_iou_distance(a_tlbr, b_tlbr):
+    """1 - IoU with cython_bbox's convention: float64, + 1 on widths, heights and intersections"""
+    a = np.asarray(a_tlbr, np.float64).reshape(-1, 4)
+    b = np.asarray(b_tlbr, np.float64).reshape(-1, 4)
+    cost = np.ones((len(a), len(b)))
+    if cost.size == 0:
+        return cost
+    area_b = (b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)
+    area_a = (a[:, 2] - a[:, 0] + 1) * (a[:, 3] - a[:, 1] + 1)
+    iw = np.minimum(a[:, None, 2], b[None, :, 2]) - np.maximum(a[:, None, 0], b[None, :, 0]) + 1
+    ih = np.minimum(a[:, None, 3], b[None, :, 3]) - np.maximum(a[:, None, 1], b[None, :, 1]) + 1
+    ok = (iw > 0) & (ih > 0)
+    inter = np.where(ok, iw * ih, 0.0)
+    return 1.0 - np.where(ok, inter / (area_a[:, None] + area_b[None, :] - inter), 0.0)
+
+
+def lapjv_assign(cost, thresh):
+    """`lap.lapjv(cost, extend_cost=True, cost_limit=thresh)` read as ByteTracker._assign reads it: the optimum of the cost matrix
+    extended with dummy rows / columns at thresh / 2 (entries may be +inf).  -> (matches [(row, col)], unmatched rows, unmatched cols)"""
+    cost = np.asarray(cost, np.float64)
+    n, m = cost.shape
+    if n == 0 or m == 0:
+        return [], list(range(n)), list(range(m))
+    ext = np.full((n + m, n + m), thresh / 2.0)
+    ext[n:, m:] = 0.0
+    ext[:n, :m] = cost
+    r, c = linear_sum_assignment(ext)
+    matches = [(int(i), int(j)) for i, j in zip(r, c) if i < n and j < m]
+    mr, mc = {i for i, _ in matches}, {j for _, j in matches}
+    return matches, [i for i in range(n) if i not in mr], [j for j in range(m) if j not in mc]
+
+
+class JDETracker:
+    """FairMOT's `JDETracker.update` with `STrack` (src/lib/tracker/multitracker.py) on the host, after the detections are decoded:
+    appearance association with Kalman gating (`fuse_motion`, lambda 0.98), IoU association of the rest, unconfirmed tracks, new
+    tracks, expiry of lost tracks after max_time_lost = int(fps / 30 * track_buffer) frames, duplicate removal.  Ids start at 1 in
+    every instance (the reference wrapper resets BaseTrack._count per call).  Float64 throughout.  Kalman filter: pp_kalman_*
+    (the same xyah filter); assignment: lapjv_assign.  Quirks kept: a lost track that expires stays one more frame in the lost
+    list (upstream subtracts the removed list before extending it), and a new track is activated at once only in frame 1.
+    A re-activated track takes the matched detection's score (the score reported is the last matched detection's).
+    Restated from memory of the published code: UNPINNED."""
+
+    CHI2INV95_4 = 9.4877
+
+    def __init__(self, frame_rate=30, conf_thres=0.2, track_buffer=30):
+        self.lib = L.load_library()
+        self.tracked, self.lost, self.removed = [], [], []
+        self.frame_id = 0
+        self.det_thresh = conf_thres
+        self.max_time_lost = int(frame_rate / 30.0 * track_buffer)
+        self._count = 0
+
+    def live_ids(self) -> set:
+        return {t.track_id for t in self.tracked + self.lost}
+
+    def _kf(self, fn, *args):
+        L.check(getattr(self.lib, fn)(*[L.ptr(a) for a in args]), fn)
+
+    def _kf_update(self, t, det):
+        self._kf("pp_kalman_update", t.mean, t.cov, det.xyah())
+
+    def _update(self, t, det):
+        t.frame_id = self.frame_id
+        t.tracklet_len += 1
+        self._kf_update(t, det)
+        t.state, t.is_activated, t.score = 1, True, det.score
+        t.update_features(det.curr_feat)
+
+    def _re_activate(self, t, det):
+        self._kf_update(t, det)
+        t.update_features(det.curr_feat)
+        t.tracklet_len, t.state, t.is_activated, t.frame_id, t.score = 0, 1, True, self.frame_id, det.score
+
+    def _activate(self, t):
+        self._count += 1
+        t.track_id = self._count
+        z = t.xyah()
+        t.mean, t.cov = np.zeros(8), np.zeros(64)
+        self._kf("pp_kalman_initiate", z, t.mean, t.cov)
+        t.tracklet_len, t.state = 0, 1
+        if self.frame_id == 1:
+            t.is_activated = True
+        t.frame_id = t.start_frame = self.frame_id
+
+    def _embedding_gated(self, pool, dets):
+        cost = np.zeros((len(pool), len(dets)))
+        if cost.size == 0:
+            return cost
+        df = np.stack([d.curr_feat for d in dets])
+        tf = np.stack([t.smooth_feat for t in pool])
+        num = tf @ df.T
+        den = np.linalg.norm(tf, axis=1)[:, None] * np.linalg.norm(df, axis=1)[None, :]
+        cost = np.maximum(0.0, 1.0 - num / den)
+        zs = np.ascontiguousarray(np.stack([d.xyah() for d in dets]))
+        for r, t in enumerate(pool):
+            g = np.zeros(len(dets))
+            L.check(self.lib.pp_kalman_gating_distance(L.ptr(t.mean), L.ptr(t.cov), L.ptr(zs), len(dets), L.ptr(g)), "pp_kalman_gating_distance")
+            cost[r, g > self.CHI2INV95_4] = np.inf
+            cost[r] = 0.98 * cost[r] + 0.02 * g
+        return cost
+
+    @staticmethod
+    def _joint(a, b):
+        ids = {t.track_id for t in a}
+        res = list(a)
+        for t in b:
+            if t.track_id not in ids:
+                ids.add(t.track_id)
+                res.append(t)
+        return res
+
+    @staticmethod
+    def _sub(a, b):
+        ids = {t.track_id for t in b}
+        return [t for t in a if t.track_id not in ids]
+
+    def step(self, dets, feats):
+        """dets [n][5] float (x1, y1, x2, y2, score) already filtered by score > conf_thres, feats [n][d]
+        -> [(track_id, tlwh float64 [4], score)] of the activated tracked tracks"""
+        self.frame_id += 1
+        dets = np.asarray(dets, np.float64).reshape(-1, 5)
+        feats = np.asarray(feats, np.float64).reshape(len(dets), -1)
+        activated, refind, lost, removed = [], [], [], []
+        detections = [_STrack(np.r_[d[:2], d[2:4] - d[:2]], d[4], f) for d, f in zip(dets, feats)]
+        unconfirmed = [t for t in self.tracked if not t.is_activated]
+        tracked = [t for t in self.tracked if t.is_activated]
+        pool = self._joint(tracked, self.lost)
+        for t in pool:                                   # multi_predict
+            if t.state != 1:
+                t.mean[7] = 0.0
+            self._kf("pp_kalman_predict", t.mean, t.cov)
+
+        def take(matches, tracks, dets_):
+            for it, idet in matches:
+                t, d = tracks[it], dets_[idet]
+                if t.state == 1:
+                    self._update(t, d)
+                    activated.append(t)
+                else:
+                    self._re_activate(t, d)
+                    refind.append(t)
+        # appearance, gated by motion
+        matches, u_track, u_det = lapjv_assign(self._embedding_gated(pool, detections), 0.4)
+        take(matches, pool, detections)
+        # IoU for the rest
+        detections = [detections[i] for i in u_det]
+        r_tracked = [pool[i] for i in u_track if pool[i].state == 1]
+        matches, u_track, u_det = lapjv_assign(jde_iou_distance([t.tlbr for t in r_tracked], [d.tlbr for d in detections]), 0.5)
+        take(matches, r_tracked, detections)
+        for it in u_track:
+            t = r_tracked[it]
+            if t.state != 2:
+                t.state = 2
+                lost.append(t)
+        # unconfirmed tracks: usually tracks with only one beginning frame
+        detections = [detections[i] for i in u_det]
+        matches, u_unc, u_det = lapjv_assign(jde_iou_distance([t.tlbr for t in unconfirmed], [d.tlbr for d in detections]), 0.7)
+        for it, idet in matches:
+            self._update(unconfirmed[it], detections[idet])
+            activated.append(unconfirmed[it])
+        for it in u_unc:
+            unconfirmed[it].state = 3
+            removed.append(unconfirmed[it])
+        for i in u_det:
+            t = detections[i]
+            if t.score < self.det_thresh:
+                continue
+            self._activate(t)
+            activated.append(t)
+        for t in self.lost:
+            if self.frame_id - t.frame_id > self.max_time_lost:
+                t.state = 3
+                removed.append(t)
+        self.tracked = [t for t in self.tracked if t.state == 1]
+        self.tracked = self._joint(self.tracked, activated)
+        self.tracked = self._joint(self.tracked, refind)
+        self.lost = self._sub(self.lost, self.tracked)
+        self.lost.extend(lost)
+        self.lost = self._sub(self.lost, self.removed)
+        self.removed.extend(removed)
+        # remove_duplicate_stracks
+        pd = jde_iou_distance([t.tlbr for t in self.tracked], [t.tlbr for t in self.lost])
+        dupa, dupb = set(), set()
+        for p, q in zip(*np.where(pd < 0.15)):
+            tp = self.tracked[p].frame_id - self.tracked[p].start_frame
+            tq = self.lost[q].frame_id - self.lost[q].start_frame
+            if tp > tq:
+                dupb.add(int(q))
+            else:
+                dupa.add(int(p))
+        self.tracked = [t for i, t in enumerate(self.tracked) if i not in dupa]
+        self.lost = [t for i, t in enumerate(self.lost) if i not in dupb]
+        return [(t.track_id, t.tlwh, t.score) for t in self.tracked if t.is_activated]
