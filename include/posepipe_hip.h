@@ -798,6 +798,57 @@ int pp_fairmot_preprocess(pp_ctx* ctx, const uint8_t* frames, int n, int src_h, 
 int pp_fairmot_decode(pp_ctx* ctx, const float* hm, const float* wh, const float* reg, const float* id, int n, int h, int w, int K,
                       int id_dim, float* dets, float* feats, int32_t* inds, int mem);
 
+/* ---- SMPL stage: VIBE (crop_affine.hip, gru.hip, smpl.hip; models/vibe.py, models/smpl.py, wrappers/vibe.py) ----------------------
+ * The device side of pose_pipeline/wrappers/vibe.py `process_vibe`.  VIBE, SPIN and smplx are not vendored: UNPINNED restatements
+ * (INTEGRATION.md); numpy / torch twins in tests/vibe_ref.py.  Added functions only: PP_ABI_VERSION stays 10.
+ *
+ * pp_warp_affine_normalize_each: pp_warp_affine_normalize with one FORWARD matrix per output sample (cv2.warpAffine(frame, M, (out_w,
+ * out_h), INTER_LINEAR), border 0, then the table): sample i is cut from frame frame_idx[i] with matrices[i] = HOST double[6] (row
+ * major 2 x 3), inverted as OpenCV inverts it.  The same fixed-point bilinear kernel.  frames [n_frames][h][w][3] u8, out
+ * [n][out_h][out_w][4], crop_u8 (optional) [n][out_h][out_w][3] in the frame's channel order; mem: where frames / out / crop_u8 live.
+ *
+ * pp_gru_forward: nn.GRU(in, hidden, num_layers = layers, batch_first), unidirectional, zero initial state, gate order r, z, n:
+ *   r = s(W_ir x + b_ir + W_hr h + b_hr), z = s(W_iz x + b_iz + W_hz h + b_hz), n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+ *   h' = (1 - z) n + z h.   x [B][T][in] -> y [B][T][hidden] = the top layer's h at every step (mem: where x and y live).
+ * params: ONE DEVICE blob, 16-byte aligned, per layer l: W_ih [3 hidden][in_l], W_hh [3 hidden][hidden], b_ih [3 hidden], b_hh
+ * [3 hidden] (in_0 = in, in_l = hidden; pp_gru_param_floats gives its length).  Per layer the input projection W_ih x + b_ih of all
+ * B T rows is one matrix product outside the recurrence; the recurrence is ONE KERNEL LAUNCH PER (layer, time step) on the context's
+ * stream -- no cooperative launch, no grid-wide barrier, no waiting on memory.  Every dot product is one wave's sum: lane q adds its
+ * terms k = q, q + 64, ... (input projection) or the 4-blocks k = 4 q, 4 q + 256, ... (recurrence) as one fmaf chain, then the 64 lane sums
+ * are added by a fixed butterfly.  The sigmoid and tanh are evaluated in double and rounded once.  Results are bit-identical from
+ * run to run and a sequence's result does not depend on B.  hidden % 4 == 0; B, T, in, layers >= 1.  With device memory the call only queues.
+ *
+ * pp_smpl_model_create: the SMPL body model, resident: v_template [V][3], shapedirs [V][3][10], posedirs [207][3 V], J_regressor
+ * [24][V], weights [V][24], J_regressor_extra [9][V] (HOST float32), vertex_ids [21] (the extra joints picked from the mesh, < V),
+ * joint_map [49] (indices into the 54 joints below).  The kinematic tree is SMPL's.
+ * pp_smpl_forward (smplx `lbs` with pose2rot = False, SPIN's joint set, VIBE's projection), per frame f of F:
+ *   v_shaped = v_template + shapedirs . betas;  J = J_regressor . v_shaped;  v_posed = v_shaped + vec(R_1..23 - I) . posedirs;
+ *   G_0 = [R_0 | J_0], G_i = G_parent [R_i | J_i - J_parent];  A_i = G_i with G_i J_i taken off its translation;
+ *   verts = (sum_i w_vi A_i) [v_posed; 1];  joints54 = (24 chain translations, verts[vertex_ids], J_regressor_extra . verts);
+ *   joints3d = joints54[joint_map];  p = joints3d + (cam1, cam2, 2 * 5000 / (224 cam0 + 1e-9));  kp2d = ((p_xy / p_z) * 5000) / 112;
+ *   pose_aa = the rotation vector of each R_i through the quaternion (torchgeometry's rotation_matrix_to_quaternion branches on the
+ *   transposed matrix with eps 1e-6, then 2 atan2(+-sin, +-cos) / sin, 2 where sin^2 == 0, NaN -> 0), evaluated in double, rounded once.
+ * Every sum (10 betas, 207 pose features, V vertices, 24 joints) is an fmaf chain or a fixed tree: no atomics, bit-identical runs.
+ * betas [F][10], rotmat [F][24][9] row major, cam [F][3] -> verts [F][V][3] (may be NULL: not returned), joints3d [F][49][3], kp2d
+ * [F][49][2], pose_aa [F][72]; mem: where all of them live (PP_MEM_HOST: staged, one stream synchronisation).
+ * pp_vibe_head_unpack: DEVICE pointers; pose6d [F][144], shape [F][shape_stride >= 10], cam_in [F][cam_stride >= 3] (the regressor
+ * program's output buffers) -> rotmat [F][24][9] (rot6d_to_rotmat: a = pose6d viewed [24][3][2], b1 = a1 / max(|a1|, 1e-12), b2 =
+ * normalised a2 - (b1 . a2) b1, b3 = b1 x b2, columns (b1, b2, b3)), betas [F][10], cam [F][3].  Queued, not synchronised. */
+typedef struct pp_smpl_model pp_smpl_model;
+int pp_warp_affine_normalize_each(pp_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const int32_t* frame_idx,
+                                  const double* matrices, int n, int out_w, int out_h, const float* lut, const int32_t* chan_map,
+                                  float* out, uint8_t* crop_u8, int mem);
+long long pp_gru_param_floats(int in, int hidden, int layers);
+int pp_gru_forward(pp_ctx* ctx, const float* x, int B, int T, int in, int hidden, int layers, const float* params, float* y, int mem);
+int pp_smpl_model_create(pp_ctx* ctx, const float* v_template, const float* shapedirs, const float* posedirs, const float* j_regressor,
+                         const float* weights, const float* j_regressor_extra, int n_verts, const int32_t* vertex_ids,
+                         const int32_t* joint_map, pp_smpl_model** out);
+void pp_smpl_model_destroy(pp_smpl_model* model);
+int pp_smpl_forward(pp_ctx* ctx, pp_smpl_model* model, const float* betas, const float* rotmat, const float* cam, int F, float* verts,
+                    float* joints3d, float* kp2d, float* pose_aa, int mem);
+int pp_vibe_head_unpack(pp_ctx* ctx, const float* pose6d, const float* shape, int shape_stride, const float* cam_in, int cam_stride,
+                        int F, float* rotmat, float* betas, float* cam);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,13 @@ SIGNATURES = {
     "pp_fairmot_input_size": (_i, [_i, _i] + [C.POINTER(C.c_int32)] * 6),
     "pp_fairmot_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "pp_fairmot_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "pp_warp_affine_normalize_each": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "pp_gru_param_floats": (C.c_longlong, [_i, _i, _i]),
+    "pp_gru_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "pp_smpl_model_create": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(_vp)]),
+    "pp_smpl_model_destroy": (None, [_vp]),
+    "pp_smpl_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
+    "pp_vibe_head_unpack": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -124,6 +124,19 @@ bool solve6(double A[6][6], double b[6], double x[6]) {
     return true;
 }
 
+// cv::warpAffine's inversion of a forward 2x3 matrix (invertAffineTransform's arithmetic, in double): dst -> src map of the kernel
+void invert_affine(double M[6], PersonXform* t) {
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1.0 / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    t->a00 = M[0]; t->a01 = M[1]; t->b0 = b1;
+    t->a10 = M[3]; t->a11 = M[4]; t->b1 = b2;
+    t->valid = 1;
+}
+
 }  // namespace
 
 // mmpose `_box2cs` + `get_affine_transform(rot=0)` + OpenCV's inversion.  Returns false for NaN boxes.
@@ -180,15 +193,7 @@ bool pp_person_transform(const double* bb, int out_w, int out_h, float cs[4], Pe
         for (double& m : M) m = 0.0;
     }
     }
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1.0 / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    t->a00 = M[0]; t->a01 = M[1]; t->b0 = b1;
-    t->a10 = M[3]; t->a11 = M[4]; t->b1 = b2;
-    t->valid = 1;
+    invert_affine(M, t);
     return true;
 }
 
@@ -215,15 +220,7 @@ void pp_center_scale_transform(const double center[2], const double scale[2], in
     }
     if (!solve6(A, b, M))
         for (double& m : M) m = 0.0;
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1.0 / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    t->a00 = M[0]; t->a01 = M[1]; t->b0 = b1;
-    t->a10 = M[3]; t->a11 = M[4]; t->b1 = b2;
-    t->valid = 1;
+    invert_affine(M, t);
 }
 
 int pp_enqueue_crop(hipStream_t s, const uint8_t* frames, int h, int w, const PersonXform* xf, int n_person,
@@ -346,6 +343,56 @@ extern "C" int pp_warp_affine_normalize(pp_ctx* ctx, const uint8_t* frames, int 
     if (mem == PP_MEM_HOST) {
         PP_HIP_CHECK(hipMemcpyAsync(out, dout, out_e * 4, hipMemcpyDeviceToHost, s));
         if (warp_u8) PP_HIP_CHECK(hipMemcpyAsync(warp_u8, dwarp, warp_b, hipMemcpyDeviceToHost, s));
+    }
+    // the staged transforms / table live in ctx scratch: finish before another call can reuse it
+    PP_HIP_CHECK(hipStreamSynchronize(s));
+    return PP_OK;
+}
+
+extern "C" int pp_warp_affine_normalize_each(pp_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const int32_t* frame_idx,
+                                             const double* matrices, int n, int out_w, int out_h, const float* lut,
+                                             const int32_t* chan_map, float* out, uint8_t* crop_u8, int mem) {
+    PP_REQUIRE(ctx && frames && frame_idx && matrices && lut && chan_map && out, "pp_warp_affine_normalize_each: NULL argument");
+    PP_REQUIRE(n_frames > 0 && h > 0 && w > 0 && out_w > 0 && out_h > 0, "pp_warp_affine_normalize_each: empty dims");
+    PP_REQUIRE(mem == PP_MEM_HOST || mem == PP_MEM_DEVICE, "pp_warp_affine_normalize_each: mem");
+    if (n <= 0) return PP_OK;
+    for (int c = 0; c < 3; ++c) PP_REQUIRE(chan_map[c] >= 0 && chan_map[c] < 3, "chan_map[%d] out of range", c);
+    std::vector<PersonXform> xf(n);
+    for (int i = 0; i < n; ++i) {
+        PP_REQUIRE(frame_idx[i] >= 0 && frame_idx[i] < n_frames, "frame_idx[%d]=%d out of range", i, frame_idx[i]);
+        double M[6];
+        for (int k = 0; k < 6; ++k) M[k] = matrices[6 * i + k];
+        invert_affine(M, &xf[i]);
+        xf[i].frame = frame_idx[i];
+    }
+    const size_t frames_b = (size_t)n_frames * h * w * 3;
+    const size_t out_e = (size_t)n * out_w * out_h * 4;
+    const size_t crop_b = crop_u8 ? (size_t)n * out_w * out_h * 3 : 0;
+    size_t need = ScratchCursor::align(n * sizeof(PersonXform)) + ScratchCursor::align(768 * sizeof(float));
+    if (mem == PP_MEM_HOST) need += ScratchCursor::align(frames_b) + ScratchCursor::align(out_e * 4) + ScratchCursor::align(crop_b);
+    int rc = ctx->ensure_scratch(need);
+    if (rc != PP_OK) return rc;
+    ScratchCursor cur(ctx);
+    hipStream_t s = ctx->stream;
+    PersonXform* dxf = cur.take<PersonXform>(n);
+    float* dlut = cur.take<float>(768);
+    PP_HIP_CHECK(hipMemcpyAsync(dxf, xf.data(), n * sizeof(PersonXform), hipMemcpyHostToDevice, s));
+    PP_HIP_CHECK(hipMemcpyAsync(dlut, lut, 768 * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint8_t* dframes = frames;
+    float* dout = out;
+    uint8_t* dcrop = crop_u8;
+    if (mem == PP_MEM_HOST) {
+        uint8_t* df = cur.take<uint8_t>(frames_b);
+        PP_HIP_CHECK(hipMemcpyAsync(df, frames, frames_b, hipMemcpyHostToDevice, s));
+        dframes = df;
+        dout = cur.take<float>(out_e);
+        if (crop_u8) dcrop = cur.take<uint8_t>(crop_b);
+    }
+    rc = pp_enqueue_crop(s, dframes, h, w, dxf, n, out_w, out_h, dlut, chan_map, 0, dout, dcrop);
+    if (rc != PP_OK) return rc;
+    if (mem == PP_MEM_HOST) {
+        PP_HIP_CHECK(hipMemcpyAsync(out, dout, out_e * 4, hipMemcpyDeviceToHost, s));
+        if (crop_u8) PP_HIP_CHECK(hipMemcpyAsync(crop_u8, dcrop, crop_b, hipMemcpyDeviceToHost, s));
     }
     // the staged transforms / table live in ctx scratch: finish before another call can reuse it
     PP_HIP_CHECK(hipStreamSynchronize(s));

@@ -199,3 +199,103 @@ def fairmot_decode(ctx: L.Context, hm_dev: int, wh_dev: int, reg_dev: int, id_de
     L.check(ctx.lib.pp_fairmot_decode(ctx.handle, C.c_void_p(hm_dev), C.c_void_p(wh_dev), C.c_void_p(reg_dev), C.c_void_p(id_dev), n, h, w,
                                       K, id_dim, L.ptr(dets), L.ptr(feats), L.ptr(inds), L.PP_MEM_HOST), "pp_fairmot_decode")
     return dets, feats, inds
+
+
+# ---- SMPL stage: VIBE (crop_affine.hip, gru.hip, smpl.hip) ---------------------------------------------------------------------------
+def warp_affine_normalize_each(ctx: L.Context, frames, frame_idx, matrices, out_wh=(224, 224), lut=None, chan_map=(0, 1, 2),
+                               want_crop_u8=False, out_dev=None, frames_dev_shape=None):
+    """cv2.warpAffine(frames[frame_idx[i]], matrices[i], out_wh, INTER_LINEAR) + the normalisation table, per sample
+    (pp_warp_affine_normalize_each).  frames: numpy [F][H][W][3] u8 -> dict(out [n][oh][ow][4] float32, crop_u8); or a device pointer
+    with frames_dev_shape = (F, H, W) and out_dev = the device address of the output (returns None; the call is synchronised)."""
+    frame_idx = np.ascontiguousarray(frame_idx, dtype=np.int32)
+    n = frame_idx.shape[0]
+    matrices = np.ascontiguousarray(matrices, dtype=np.float64).reshape(n, 6)
+    lut = normalize_lut() if lut is None else np.ascontiguousarray(lut, np.float32)
+    cm = np.asarray(chan_map, dtype=np.int32)
+    ow, oh = out_wh
+    if isinstance(frames, np.ndarray):
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        f, h, w, c = frames.shape
+        assert c == 3
+        out = np.empty((n, oh, ow, 4), np.float32)
+        crop = np.empty((n, oh, ow, 3), np.uint8) if want_crop_u8 else None
+        L.check(ctx.lib.pp_warp_affine_normalize_each(ctx.handle, L.ptr(frames), f, h, w, L.ptr(frame_idx), L.ptr(matrices), n, ow, oh,
+                                                      L.ptr(lut), L.ptr(cm), L.ptr(out), L.ptr(crop), L.PP_MEM_HOST), "pp_warp_affine_normalize_each")
+        return dict(out=out, crop_u8=crop)
+    f, h, w = frames_dev_shape
+    L.check(ctx.lib.pp_warp_affine_normalize_each(ctx.handle, C.c_void_p(int(frames)), f, h, w, L.ptr(frame_idx), L.ptr(matrices), n, ow, oh,
+                                                  L.ptr(lut), L.ptr(cm), C.c_void_p(int(out_dev)), None, L.PP_MEM_DEVICE), "pp_warp_affine_normalize_each")
+    return None
+
+
+def gru_param_blob(layers_params) -> np.ndarray:
+    """[(W_ih [3H][in_l], W_hh [3H][H], b_ih [3H], b_hh [3H]), ...] per layer (nn.GRU's weight_ih_l{k} ... in its own order) -> the
+    flat float32 blob pp_gru_forward reads"""
+    return np.concatenate([np.asarray(a, np.float32).reshape(-1) for layer in layers_params for a in layer])
+
+
+class Gru:
+    """nn.GRU(in, hidden, layers) with its parameters resident on the device (pp_gru_forward)"""
+
+    def __init__(self, ctx: L.Context, layers_params):
+        self.ctx = ctx
+        self.layers = len(layers_params)
+        self.hidden = int(np.shape(layers_params[0][1])[1])
+        self.inp = int(np.shape(layers_params[0][0])[1])
+        blob = gru_param_blob(layers_params)
+        assert blob.size == ctx.lib.pp_gru_param_floats(self.inp, self.hidden, self.layers), blob.size
+        self.params = ctx.malloc(blob.nbytes)
+        ctx.h2d(self.params, blob)
+
+    def forward(self, x) -> np.ndarray:
+        """x [B][T][in] numpy -> y [B][T][hidden]"""
+        x = np.ascontiguousarray(x, np.float32)
+        b, t, i = x.shape
+        assert i == self.inp
+        y = np.empty((b, t, self.hidden), np.float32)
+        L.check(self.ctx.lib.pp_gru_forward(self.ctx.handle, L.ptr(x), b, t, i, self.hidden, self.layers, C.c_void_p(self.params), L.ptr(y),
+                                            L.PP_MEM_HOST), "pp_gru_forward")
+        return y
+
+    def forward_dev(self, x_dev: int, b: int, t: int, y_dev: int):
+        """device x [b][t][in] -> device y [b][t][hidden]; queued on the context's stream"""
+        L.check(self.ctx.lib.pp_gru_forward(self.ctx.handle, C.c_void_p(x_dev), b, t, self.inp, self.hidden, self.layers,
+                                            C.c_void_p(self.params), C.c_void_p(y_dev), L.PP_MEM_DEVICE), "pp_gru_forward")
+
+    def close(self):
+        if getattr(self, "params", None) and getattr(self.ctx, "handle", None):
+            self.ctx.free(self.params)
+        self.params = None
+
+
+class SmplModel:
+    """the SMPL body model resident on the device (pp_smpl_model_create / pp_smpl_forward); `body`: the arrays of models/smpl.py"""
+
+    def __init__(self, ctx: L.Context, body: dict, vertex_ids, joint_map):
+        self.ctx = ctx
+        f32 = lambda k: np.ascontiguousarray(body[k], np.float32)                 # noqa: E731
+        self.n_verts = int(body["v_template"].shape[0])
+        ids, jm = np.ascontiguousarray(vertex_ids, np.int32), np.ascontiguousarray(joint_map, np.int32)
+        assert ids.shape == (21,) and jm.shape == (49,)
+        h = C.c_void_p()
+        L.check(ctx.lib.pp_smpl_model_create(ctx.handle, L.ptr(f32("v_template")), L.ptr(f32("shapedirs")), L.ptr(f32("posedirs")),
+                                             L.ptr(f32("J_regressor")), L.ptr(f32("weights")), L.ptr(f32("J_regressor_extra")), self.n_verts,
+                                             L.ptr(ids), L.ptr(jm), C.byref(h)), "pp_smpl_model_create")
+        self.handle = h
+
+    def forward(self, betas, rotmat, cam, want_verts=True) -> dict:
+        """betas [F][10], rotmat [F][24][3][3], cam [F][3] numpy -> dict(verts [F][V][3] or None, joints3d [F][49][3], kp2d [F][49][2],
+        pose_aa [F][72])"""
+        betas, rotmat, cam = (np.ascontiguousarray(a, np.float32) for a in (betas, rotmat, cam))
+        f = betas.shape[0]
+        assert betas.shape == (f, 10) and rotmat.size == f * 216 and cam.shape == (f, 3)
+        verts = np.empty((f, self.n_verts, 3), np.float32) if want_verts else None
+        j3, k2, aa = np.empty((f, 49, 3), np.float32), np.empty((f, 49, 2), np.float32), np.empty((f, 72), np.float32)
+        L.check(self.ctx.lib.pp_smpl_forward(self.ctx.handle, self.handle, L.ptr(betas), L.ptr(rotmat), L.ptr(cam), f, L.ptr(verts), L.ptr(j3),
+                                             L.ptr(k2), L.ptr(aa), L.PP_MEM_HOST), "pp_smpl_forward")
+        return dict(verts=verts, joints3d=j3, kp2d=k2, pose_aa=aa)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.pp_smpl_model_destroy(self.handle)
+            self.handle = None

@@ -421,6 +421,66 @@ class LiftingPerson(dj.Computed):  # pipeline.py:1252-1257
                 "Right wrist"]
 
 
+# ---- SMPL stage (pipeline.py:1513-1640) ----------------------------------------------------------------------------------
+@schema
+class SMPLMethodLookup(dj.Lookup):  # pipeline.py:1515-1530
+    definition = """
+    smpl_method       : int
+    ---
+    smpl_method_name  : varchar(50)
+    """
+    contents = [
+        {"smpl_method": 0, "smpl_method_name": "VIBE"},
+        {"smpl_method": 1, "smpl_method_name": "MEVA"},
+        {"smpl_method": 2, "smpl_method_name": "ProHMR"},
+        {"smpl_method": 3, "smpl_method_name": "Expose"},
+        {"smpl_method": 4, "smpl_method_name": "PARE"},
+        {"smpl_method": 5, "smpl_method_name": "PIXIE"},
+        {"smpl_method": 6, "smpl_method_name": "ProHMR_MMPose"},
+        {"smpl_method": 7, "smpl_method_name": "HybrIK"},
+    ]
+
+
+@schema
+class SMPLMethod(dj.Manual):  # pipeline.py:1534-1538
+    definition = """
+    -> PersonBbox
+    -> SMPLMethodLookup
+    """
+
+
+@schema
+class SMPLPerson(dj.Computed):  # pipeline.py:1542-1552
+    definition = """
+    -> SMPLMethod
+    ---
+    model_type      : varchar(50)
+    cams            : longblob
+    poses           : longblob
+    betas           : longblob
+    joints3d        : longblob
+    joints2d        : longblob
+    """
+
+    def make(self, key):  # pipeline.py:1556-1620
+        name = (SMPLMethodLookup & key).fetch1("smpl_method_name")
+        if name == "VIBE":
+            from .wrappers.vibe import process_vibe
+            res = process_vibe(key)
+            res["model_type"] = "SMPL"
+        else:                                   # MEVA, ProHMR, Expose, PARE, PIXIE, ProHMR_MMPose, HybrIK: not built
+            raise Exception(f"Method {name} not implemented")
+        res.pop("verts", None)                  # :1617-1618: the mesh is computed but not stored
+        self.insert1(res)
+
+    @staticmethod
+    def joint_names(model="smpl"):  # pipeline.py:1622-1631
+        if model.upper() == "SMPL":
+            from .models.smpl import JOINT_NAMES_49
+            return list(JOINT_NAMES_49)
+        raise NotImplementedError(f"joint names of model {model!r}: only the SMPL methods' 49 joints are built")
+
+
 # ---- hand stage (pipeline.py:1979-2146) --------------------------------------------------------------------------------
 @schema
 class HandBboxMethodLookup(dj.Lookup):  # pipeline.py:1980-1990

@@ -1,7 +1,7 @@
 """Recipes over the hot-path tables: video key -> tracking -> person box -> top-down 2D -> 3D lifting.
 
 Same entry points, arguments and return values as the reference's recipes
-(pose_pipeline/utils/standard_pipelines.py:10 `tracking_pipeline`, :56 `top_down_pipeline`, :110 `lifting_pipeline`;
+(pose_pipeline/utils/standard_pipelines.py:10 `tracking_pipeline`, :56 `top_down_pipeline`, :110 `lifting_pipeline`, :167 `smpl_pipeline`;
 pose_pipeline/utils/tracking.py:5 `annotate_single_person`), so `scripts/process_h36m.py`-style callers run unchanged.
 The bodies are this package's own: every recipe is a walk over the declarative `STAGES` table below (lookup table ->
 method table -> computed tables), so adding a stage or a method is a table entry, not another copy of the sequence.
@@ -12,7 +12,8 @@ The DEFAULTS are the reference's own (utils/standard_pipelines.py:12,58-59,112-1
     the default fails in the lookup's fetch1, exactly like the reference; callers pass "MMPose" / "MMPoseHalpe" / ...
     (scripts/process_h36m.py does);
   * lifting_method_name "GastNet" -- a lookup row whose wrapper is outside the hot path:
-    LiftingPerson.make raises for it; callers of the hot path pass "VideoPose3D".
+    LiftingPerson.make raises for it; callers of the hot path pass "VideoPose3D";
+  * smpl_method_name "PIXIE" -- a lookup row that is not built: SMPLPerson.make raises "not implemented"; callers pass "VIBE".
 A method name that is not in its lookup table raises from fetch1 (no silent substitution).  `BestDetectedFrames` is populated
 where the reference populates it (:100, :162); the OpenPose branch (:95-97, SURVEY.md section 2, out of scope) is not part of
 the walk.
@@ -54,6 +55,7 @@ STAGES = {
     "tracking": Stage("tracking_method", P.TrackingBboxMethodLookup, P.TrackingBboxMethod, (P.TrackingBbox,)),
     "top_down": Stage("top_down_method", P.TopDownMethodLookup, P.TopDownMethod, (P.TopDownPerson,)),
     "lifting": Stage("lifting_method", P.LiftingMethodLookup, P.LiftingMethod, (P.LiftingPerson,)),
+    "smpl": Stage("smpl_method", P.SMPLMethodLookup, P.SMPLMethod, (P.SMPLPerson,)),
 }
 
 
@@ -140,3 +142,29 @@ def lifting_pipeline(key, tracking_method_name: str = "DeepSortYOLOv4", top_down
     for table in (P.VideoInfo, P.DetectedFrames, P.BestDetectedFrames):
         table.populate(key, reserve_jobs=reserve_jobs)
     return len(P.LiftingPerson & key) > 0
+
+
+def smpl_pipeline(key: Union[Dict, List[Dict]], tracking_method_name: str = "DeepSortYOLOv4", smpl_method_name: str = "PIXIE",
+                  reserve_jobs: bool = False):
+    """... -> the subject's SMPL parameters and joints (utils/standard_pipelines.py:167-206).  Returns the SMPLPerson keys that exist
+    afterwards; False as soon as a video has no person box (its subject is not annotated yet, or was marked invalid with a negative
+    video_subject_id)."""
+    videos = _as_list(key)
+    tracking_pipeline(videos, tracking_method_name, reserve_jobs=reserve_jobs)
+    tracking_method = STAGES["tracking"].method_id(tracking_method_name)
+    out = []
+    for video_key in videos:
+        tracking_key = {**video_key, "tracking_method": tracking_method}
+        person = _person_key(tracking_key)
+        if person is None:
+            marked = P.PersonBboxValid & tracking_key
+            if len(marked) == 1 and marked.fetch1("video_subject_id") < 0:
+                print(f"{tracking_key}: marked invalid, skipped")
+            else:
+                print(f"{tracking_key}: no subject of interest annotated yet")
+            return False
+        smpl_key = STAGES["smpl"].enter(person, smpl_method_name)
+        STAGES["smpl"].run(smpl_key, reserve_jobs)
+        if len(P.SMPLPerson & smpl_key) == 1:
+            out.append(smpl_key)
+    return out

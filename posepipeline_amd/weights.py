@@ -19,8 +19,9 @@ def model_data_dir() -> str:
     return os.environ.get("PIPELINE_3RDPARTY", os.path.join(_PKG, "..", "3rdparty"))
 
 
-def load_state_dict(path: str, key_candidates=("state_dict", "model_pos")) -> dict:
-    """torch checkpoint (.pth / .bin) -> {name: float32 numpy array}."""
+def load_state_dict(path: str, key_candidates=("state_dict", "model_pos", "model", "gen_state_dict")) -> dict:
+    """torch checkpoint (.pth / .bin) -> {name: float32 numpy array}.  key_candidates: the dict keys a checkpoint may keep its state dict
+    under (mm*: `state_dict`, VideoPose3D / PoseFormer: `model_pos`, SPIN: `model`, VIBE: `gen_state_dict`); the first one present wins."""
     import torch
     ckpt = torch.load(path, map_location="cpu")
     sd = ckpt
