@@ -849,6 +849,50 @@ int pp_smpl_forward(pp_ctx* ctx, pp_smpl_model* model, const float* betas, const
 int pp_vibe_head_unpack(pp_ctx* ctx, const float* pose6d, const float* shape, int shape_stride, const float* cam_in, int cam_stride,
                         int F, float* rotmat, float* betas, float* cam);
 
+/* ---- TraDeS (trades.hip, fairmot.hip; models/trades.py, tracking.TradesTracker) ----------------------------------------------------
+ * The device side of TrackingBboxMethodLookup row 4 besides the layers of models/dla.py.  TraDeS and CenterTrack are not vendored:
+ * UNPINNED restatements; numpy twins in tests/trades_ref.py.  Added functions and op types over existing pp_op
+ * fields only: sizeof(pp_op) is unchanged and PP_ABI_VERSION stays 10.
+ *
+ * pp_trades_cva: cost-volume association of n frame pairs.  emb_cur, emb_prev [n][hc][wc][128] float32 (P = hc wc cells).  With
+ *   c[q][i][j] = <emb_cur[q], emb_prev[i][j]> (128 terms, ONE fmaf chain in channel order from 0: the float32-input MFMA, exact float32),
+ *   ch[q][i] = max_j c[q][i][j],  cw[q][j] = max_i c[q][i][j]   (selections: exact),
+ *   soft_h[q][.] = softmax_i(5 ch[q][.]),  soft_w[q][.] = softmax_j(5 cw[q][.]):  x = 5.f * v (float32), m = max x, e = exp(x - m) with
+ *   x - m rounded to float32 and exp EVALUATED IN DOUBLE AND ROUNDED ONCE, s = sum e, p = e / s;
+ *   off_h[q] = sum_i p_i * float(2 (i - i_q)),  off_w[q] = sum_j p_j * float(2 (j - j_q)),  q = (i_q, j_q).
+ *   Sums: lane k of one wave adds its terms k, k + 64, ... in that order, then the 64 lane sums by a fixed butterfly; bit-identical
+ *   from run to run.  offset [n][2 hc][2 wc][2]: channel 0 = off_w, channel 1 = off_h, each value written to the 2 x 2 block of its cell
+ *   (nearest x2).  soft_h [n][P][hc] and soft_w [n][P][wc]: optional (both or neither).  The P x P volume is never written to global
+ *   memory.  mem: where every pointer lives (PP_MEM_HOST: staged, one stream synchronisation; device: only queued).  hc + wc <= 510.
+ *
+ * pp_trades_render_prehm: CenterTrack's pre_hm after AvgPool2d(4, 4).  boxes: HOST int32 [n_boxes][3] = (cx, cy, radius) in
+ *   network-input pixels, computed by the caller in the reference's float arithmetic (models/trades.prehm_boxes).  Input-resolution
+ *   map (never stored): pixel (x, y) = max over the boxes with |x - cx| <= r and |y - cy| <= r of g = exp(-((x - cx)^2 + (y - cy)^2) /
+ *   (2 sigma^2)), sigma = (2 r + 1) / 6, EVALUATED IN DOUBLE AND ROUNDED ONCE to float32, g < 2^-52 -> 0 (draw_umich_gaussian; the
+ *   patch is clipped to the map by construction), 0 where no box reaches.  out [hp / 4][wp / 4] = float32 sum of the 4 x 4 pixels in
+ *   (ky, kx) order / 16 (PP_OP_AVGPOOL's rule); mem: where out lives.  hp, wp multiples of 4.  One stream synchronisation.
+ *
+ * pp_trades_decode: head maps, DEVICE pointers, NHWC: hm [n][h][w][1] logits, reg [n][h][w][2], ltrb [n][h][w][4] (ltrb_amodal),
+ *   tracking [n][h][w][2].  Peaks, scores, ranking and the equal-score rule (LOWER FLAT INDEX FIRST) are pp_fairmot_decode's.
+ *   dets [n][K][9] = (x + reg0, y + reg1,  x + l, y + t, x + r, y + b  (amodal, about the INTEGER peak),  tracking0, tracking1,  score);
+ *   inds [n][K].  Slots beyond the number of peaks hold index -1 and zeros.  mem: where dets / inds live.
+ *
+ * Three op types of program B (the per-frame half of the network; trades.hip):
+ * PP_OP_SUB_CAT: out[y][x] = (in2[y][x][0 .. c2), 0 ..., in[y][x][c] - res1[y][x][c]): in, res1 [h][w][cin], in2 [h][w][c2], c2 <= 4,
+ *   out [h][w][4 + cin]; channels [c2, 4) are zeros; cin = the map's channels, cout = 4 + cin, cin % 4 == 0.
+ * PP_OP_BCAST_MUL: out[y][x][c] = in2[y][x][0] * in[y][x][c]: in, out [h][w][cin], in2 [h][w][1]; cin = cout % 4 == 0.
+ * PP_OP_BLEND2: out[y][x][c] = a0 in[y][x][c] + a1 res1[y][x][c], (a0, a1) = softmax(in2[y][x][0], in3[y][x][0]): m = max, e_k =
+ *   exp(l_k - m) evaluated in double and rounded once, a_k = e_k / (e_0 + e_1) (float32); the two products rounded, then added.
+ *   in, res1, out [h][w][cin]; in2, in3 [h][w][1]; cin = cout % 4 == 0.  Every other field keeps its neutral value. */
+#define PP_OP_SUB_CAT 18
+#define PP_OP_BCAST_MUL 19
+#define PP_OP_BLEND2 20
+int pp_trades_cva(pp_ctx* ctx, const float* emb_cur, const float* emb_prev, int n, int hc, int wc, int dim, float* offset,
+                  float* soft_h, float* soft_w, int mem);
+int pp_trades_render_prehm(pp_ctx* ctx, const int32_t* boxes, int n_boxes, int hp, int wp, float* out, int mem);
+int pp_trades_decode(pp_ctx* ctx, const float* hm, const float* reg, const float* ltrb, const float* tracking, int n, int h, int w,
+                     int K, float* dets, int32_t* inds, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -471,8 +471,11 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
     PP_REQUIRE(op.in >= 0 && op.in < nb && op.out >= 0 && op.out < nb, "op %d: buffer id out of range", idx);
     PP_REQUIRE(op.res1 < nb && op.res2 < nb, "op %d: residual buffer id out of range", idx);
     PP_REQUIRE(op.in2 < nb && op.in3 < nb && (op.type == PP_OP_UPSAMPLE_ADD || op.type == PP_OP_BILINEAR_ADD ||
-                                              (op.type == PP_OP_DCN3X3 && op.in3 < 0) || (op.in2 < 0 && op.in3 < 0)),
-               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD / PP_OP_BILINEAR_ADD (in2: PP_OP_DCN3X3) only (-1 elsewhere)", idx);
+                                              (op.type == PP_OP_DCN3X3 && op.in3 < 0) || op.type == PP_OP_BLEND2 ||
+                                              ((op.type == PP_OP_SUB_CAT || op.type == PP_OP_BCAST_MUL) && op.in3 < 0) ||
+                                              (op.in2 < 0 && op.in3 < 0)),
+               "op %d: in2 / in3 are inputs of PP_OP_UPSAMPLE_ADD / PP_OP_BILINEAR_ADD / PP_OP_BLEND2 (in2: PP_OP_DCN3X3 / PP_OP_SUB_CAT / "
+               "PP_OP_BCAST_MUL) only (-1 elsewhere)", idx);
     const pp_buf& bi = net.bufs[op.in];
     const pp_buf& bo = net.bufs[op.out];
     const int eh = op.pad_end & 1, ew = (op.pad_end >> 1) & 1;   // TensorFlow SAME: the odd padding row / column goes last
@@ -636,6 +639,22 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
                        "op %d: dwdeconv res1 must be a [h s][w s][c] buffer other than out", idx);
         PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)op.kh * op.kw * op.cout <= net.n_weights,
                    "op %d: dwdeconv parameters out of blob", idx);
+    } else if (op.type == PP_OP_SUB_CAT || op.type == PP_OP_BCAST_MUL || op.type == PP_OP_BLEND2) {
+        const bool cat = op.type == PP_OP_SUB_CAT;
+        PP_REQUIRE(op.cin > 0 && (op.cin & 3) == 0 && bi.c == op.cin && op.cout == op.cin + (cat ? 4 : 0) && bo.c == op.cout && bo.h == bi.h &&
+                       bo.w == bi.w && op.in != op.out,
+                   "op %d: needs in [h][w][cin %% 4 == 0] and a distinct out [h][w][cout], cout = cin (sub_cat: cin + 4)", idx);
+        PP_REQUIRE(op.res2 < 0 && !op.out_nchw && op.out_c_off == 0 && op.in_c_off == 0 && op.up_log2 == 0 && op.relu == PP_RELU_NONE,
+                   "op %d: no res2, slices, upsampling or activation", idx);
+        PP_REQUIRE((op.type == PP_OP_BCAST_MUL) == (op.res1 < 0), "op %d: sub_cat and blend2 take their second map in res1, bcast_mul takes none", idx);
+        if (op.res1 >= 0)
+            PP_REQUIRE(net.bufs[op.res1].c == bi.c && net.bufs[op.res1].h == bi.h && net.bufs[op.res1].w == bi.w && op.res1 != op.out,
+                       "op %d: res1 must be a [h][w][cin] buffer other than out", idx);
+        PP_REQUIRE(op.in2 >= 0 && (op.type == PP_OP_BLEND2) == (op.in3 >= 0), "op %d: in2 (blend2: and in3) must be given", idx);
+        for (int b : {op.in2, op.in3})
+            if (b >= 0)
+                PP_REQUIRE(net.bufs[b].h == bi.h && net.bufs[b].w == bi.w && b != op.out && (cat ? net.bufs[b].c >= 1 && net.bufs[b].c <= 4 : net.bufs[b].c == 1),
+                           "op %d: in2 / in3 must be [h][w][1] maps (sub_cat: [h][w][1 .. 4]) other than out", idx);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         PP_REQUIRE(op.cin == op.cout && bi.c == op.cin && bo.c == op.cin && bi.h == bo.h && bi.w == bo.w && op.in != op.out,
                    "op %d: vit encoder needs distinct in / out buffers of [h][w][dim]", idx);
@@ -753,6 +772,14 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
     } else if (op.type == PP_OP_DWDECONV) {
         return pp_launch_dwdeconv(net->buf_ptr(op.in), net->weights + op.w_off, op.res1 >= 0 ? net->buf_ptr(op.res1) : nullptr,
                                   net->buf_ptr(op.out), batch, bi.h, bi.w, op.cout, op.stride, s);
+    } else if (op.type == PP_OP_SUB_CAT) {
+        return pp_launch_sub_cat(net->buf_ptr(op.in), net->buf_ptr(op.res1), net->buf_ptr(op.in2), net->buf_ptr(op.out),
+                                 (size_t)batch * bi.h * bi.w, op.cin, net->bufs[op.in2].c, s);
+    } else if (op.type == PP_OP_BCAST_MUL) {
+        return pp_launch_bcast_mul(net->buf_ptr(op.in), net->buf_ptr(op.in2), net->buf_ptr(op.out), (size_t)batch * bi.h * bi.w, op.cin, s);
+    } else if (op.type == PP_OP_BLEND2) {
+        return pp_launch_blend2(net->buf_ptr(op.in), net->buf_ptr(op.res1), net->buf_ptr(op.in2), net->buf_ptr(op.in3), net->buf_ptr(op.out),
+                                (size_t)batch * bi.h * bi.w, op.cin, s);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         pp_vit_encoder* enc = net->vits[&op - net->ops.data()];
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);

@@ -383,6 +383,20 @@ __global__ __launch_bounds__(256) void fm_peaks_kernel(const float* __restrict__
     }
 }
 
+// rank of `key` among the np keys of a frame = the number of larger keys (the equal-score rule lives in the key); sh: 256 LDS slots;
+// called by every thread of a 256-thread workgroup
+__device__ __forceinline__ int fm_rank_of(const unsigned long long* __restrict__ kf, int np, unsigned long long key, unsigned long long* sh) {
+    int rank = 0;
+    for (int base = 0; base < np; base += 256) {
+        sh[threadIdx.x] = base + (int)threadIdx.x < np ? kf[base + threadIdx.x] : 0ull;
+        __syncthreads();
+        const int lim = np - base < 256 ? np - base : 256;
+        for (int j = 0; j < lim; ++j) rank += sh[j] > key;
+        __syncthreads();
+    }
+    return rank;
+}
+
 __global__ __launch_bounds__(256) void fm_rank_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ cnt, int h, int w,
                                                       int K, const float* __restrict__ wh, const float* __restrict__ reg,
                                                       float* __restrict__ dets, int* __restrict__ inds) {
@@ -392,14 +406,7 @@ __global__ __launch_bounds__(256) void fm_rank_kernel(const unsigned long long* 
     const unsigned long long* kf = keys + (size_t)f * hw;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long key = i < np ? kf[i] : ~0ull;
-    int rank = 0;
-    for (int base = 0; base < np; base += 256) {
-        sh[threadIdx.x] = base + (int)threadIdx.x < np ? kf[base + threadIdx.x] : 0ull;
-        __syncthreads();
-        const int lim = np - base < 256 ? np - base : 256;
-        for (int j = 0; j < lim; ++j) rank += sh[j] > key;
-        __syncthreads();
-    }
+    const int rank = fm_rank_of(kf, np, key, sh);
     if (i < np && rank < K) {
         const int p = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
         const int y = p / w, x = p - y * w;
@@ -435,10 +442,10 @@ __global__ __launch_bounds__(64) void fm_feats_kernel(const float* __restrict__ 
     for (int c = lane; c < dim; c += 64) o[c] = v[c] / nrm;
 }
 
-__global__ __launch_bounds__(256) void fm_fill_kernel(float* __restrict__ dets, int* __restrict__ inds, size_t slots) {
+__global__ __launch_bounds__(256) void fm_fill_kernel(float* __restrict__ dets, int* __restrict__ inds, size_t slots, int width) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x) {
         inds[i] = -1;
-        for (int k = 0; k < 5; ++k) dets[i * 5 + k] = 0.f;
+        for (int k = 0; k < width; ++k) dets[i * width + k] = 0.f;
     }
 }
 
@@ -560,7 +567,7 @@ int pp_fairmot_decode(pp_ctx* ctx, const float* hm, const float* wh, const float
     PP_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
     // slots beyond the number of peaks: index -1, zeros (torch.topk fills them with zero-valued non-peaks in an unspecified
     // order; their score 0 is below every confidence threshold)
-    hipLaunchKernelGGL(fm_fill_kernel, dim3(grid_for(slots, 256)), dim3(256), 0, s, d_dets, d_inds, slots);
+    hipLaunchKernelGGL(fm_fill_kernel, dim3(grid_for(slots, 256)), dim3(256), 0, s, d_dets, d_inds, slots, 5);
     hipLaunchKernelGGL(fm_sigmoid_kernel, dim3(grid_for(n * hw, 256)), dim3(256), 0, s, hm, sig, n * hw);
     const dim3 grid((unsigned)((hw + 255) / 256), n);
     hipLaunchKernelGGL(fm_peaks_kernel, grid, dim3(256), 0, s, sig, h, w, keys, cnt);
@@ -577,3 +584,71 @@ int pp_fairmot_decode(pp_ctx* ctx, const float* hm, const float* wh, const float
 }
 
 }  // extern "C"
+
+// ---- pp_trades_decode (TraDeS, wrappers/trades.py): the peak, key and rank scheme above with CenterTrack's outputs ---------------
+namespace {
+
+__global__ __launch_bounds__(256) void trades_rank_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ cnt, int h, int w,
+                                                         int K, const float* __restrict__ reg, const float* __restrict__ ltrb,
+                                                         const float* __restrict__ trk, float* __restrict__ dets, int* __restrict__ inds) {
+    __shared__ unsigned long long sh[256];
+    const int hw = h * w, f = blockIdx.y, np = cnt[f];
+    if ((int)(blockIdx.x * blockDim.x) >= np) return;            // uniform per workgroup
+    const unsigned long long* kf = keys + (size_t)f * hw;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long key = i < np ? kf[i] : ~0ull;
+    const int rank = fm_rank_of(kf, np, key, sh);
+    if (i < np && rank < K) {
+        const int p = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+        const int y = p / w, x = p - y * w;
+        const float* r = reg + ((size_t)f * hw + p) * 2;
+        const float* q = ltrb + ((size_t)f * hw + p) * 4;
+        const float* t = trk + ((size_t)f * hw + p) * 2;
+        float* d = dets + ((size_t)f * K + rank) * 9;
+        d[0] = (float)x + r[0];
+        d[1] = (float)y + r[1];
+        d[2] = (float)x + q[0];
+        d[3] = (float)y + q[1];
+        d[4] = (float)x + q[2];
+        d[5] = (float)y + q[3];
+        d[6] = t[0];
+        d[7] = t[1];
+        d[8] = __uint_as_float((unsigned)(key >> 32));
+        inds[(size_t)f * K + rank] = p;
+    }
+}
+
+}  // namespace
+
+extern "C" int pp_trades_decode(pp_ctx* ctx, const float* hm, const float* reg, const float* ltrb, const float* tracking, int n, int h, int w,
+                                int K, float* dets, int32_t* inds, int mem) {
+    PP_REQUIRE(ctx && hm && reg && ltrb && tracking && dets && inds, "pp_trades_decode: NULL argument");
+    PP_REQUIRE(n > 0 && h > 0 && w > 0 && K > 0 && (long long)K <= (long long)h * w && (long long)n * h * w < (1ll << 31),
+               "pp_trades_decode needs 0 < K <= h * w");
+    const size_t hw = (size_t)h * w, slots = (size_t)n * K;
+    const bool host = mem == PP_MEM_HOST;
+    size_t need = ScratchCursor::align(n * hw * 4) + ScratchCursor::align(n * hw * 8) + ScratchCursor::align((size_t)n * 4);
+    if (host) need += ScratchCursor::align(slots * 9 * 4) + ScratchCursor::align(slots * 4);
+    int rc = ctx->ensure_scratch(need);
+    if (rc != PP_OK) return rc;
+    ScratchCursor cur(ctx);
+    float* sig = cur.take<float>(n * hw);
+    unsigned long long* keys = cur.take<unsigned long long>(n * hw);
+    int* cnt = cur.take<int>(n);
+    float* d_dets = host ? cur.take<float>(slots * 9) : dets;
+    int* d_inds = host ? cur.take<int>(slots) : inds;
+    hipStream_t s = ctx->stream;
+    PP_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(fm_fill_kernel, dim3(grid_for(slots, 256)), dim3(256), 0, s, d_dets, d_inds, slots, 9);
+    hipLaunchKernelGGL(fm_sigmoid_kernel, dim3(grid_for(n * hw, 256)), dim3(256), 0, s, hm, sig, n * hw);
+    const dim3 grid((unsigned)((hw + 255) / 256), n);
+    hipLaunchKernelGGL(fm_peaks_kernel, grid, dim3(256), 0, s, sig, h, w, keys, cnt);
+    hipLaunchKernelGGL(trades_rank_kernel, grid, dim3(256), 0, s, keys, cnt, h, w, K, reg, ltrb, tracking, d_dets, d_inds);
+    PP_HIP_CHECK(hipGetLastError());
+    if (host) {
+        PP_HIP_CHECK(hipMemcpyAsync(dets, d_dets, slots * 9 * 4, hipMemcpyDeviceToHost, s));
+        PP_HIP_CHECK(hipMemcpyAsync(inds, d_inds, slots * 4, hipMemcpyDeviceToHost, s));
+        PP_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return PP_OK;
+}

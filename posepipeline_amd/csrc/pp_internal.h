@@ -265,6 +265,11 @@ int pp_dcn3x3_max_cout();
 // x [n][h][w][c], wgt [2 s][2 s][c], res (may be null) and y [n][h s][w s][c]
 int pp_launch_dwdeconv(const float* x, const float* wgt, const float* res, float* y, int n, int h, int w, int c, int stride,
                        hipStream_t stream);
+// ---- PP_OP_SUB_CAT / PP_OP_BCAST_MUL / PP_OP_BLEND2 (trades.hip; field by field in posepipe_hip.h) -----------------------------
+// y [pixels][4 + c] = (lead [pixels][c2 <= 4], zeros, a - b);  y = g [pixels][1] * x;  y = softmax(l0, l1) . (x0, x1)
+int pp_launch_sub_cat(const float* a, const float* b, const float* lead, float* y, size_t pixels, int c, int c2, hipStream_t stream);
+int pp_launch_bcast_mul(const float* x, const float* g, float* y, size_t pixels, int c, hipStream_t stream);
+int pp_launch_blend2(const float* x0, const float* x1, const float* l0, const float* l1, float* y, size_t pixels, int c, hipStream_t stream);
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

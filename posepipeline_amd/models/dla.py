@@ -101,8 +101,8 @@ def _dla_up_plan():
     return plan
 
 
-def dla34_param_shapes() -> dict:
-    """{upstream state-dict key: shape} of every parameter the inference pass reads"""
+def dla34_trunk_param_shapes() -> dict:
+    """{upstream state-dict key: shape} of base, dla_up and ida_up: everything in front of the heads (shared with models/trades.py)"""
     s: dict = {}
     s["base.base_layer.0.weight"] = (16, 3, 7, 7)
     _bn(s, "base.base_layer.1", 16)
@@ -115,6 +115,12 @@ def dla34_param_shapes() -> dict:
     for i, (o, chans, up_f) in enumerate(_dla_up_plan()):
         _ida(s, f"dla_up.ida_{i}", o, chans, up_f)
     _ida(s, "ida_up", 64, [64, 128, 256], [1, 2, 4])
+    return s
+
+
+def dla34_param_shapes() -> dict:
+    """{upstream state-dict key: shape} of every parameter the inference pass reads"""
+    s = dla34_trunk_param_shapes()
     for head, c in HEADS:
         s[f"{head}.0.weight"] = (HEAD_CONV, 64, 3, 3)
         s[f"{head}.0.bias"] = (HEAD_CONV,)
@@ -186,11 +192,10 @@ def get_state_dict(seed: int = 11) -> dict:
     return weights.get_state_dict(CHECKPOINT, dla34_param_shapes(), seed=seed, synth=synth_dla34_state_dict)
 
 
-def build_dla34_program(sd: dict, hp: int, wp: int, keep=()) -> Program:
-    """hp, wp: network input size, multiples of 32.  keep: op names whose outputs keep a buffer of their own, found under that
-    name in Program.named (tests and profiles that read an intermediate map)"""
+def dla34_trunk(pb: ProgramBuilder, sd: dict, hp: int, wp: int) -> int:
+    """base, dla_up and ida_up on the builder's new "input" buffer [hp][wp][4] -> the 64-channel stride-4 feature map (virtual
+    buffer).  hp, wp: multiples of 32."""
     assert hp % 32 == 0 and wp % 32 == 0, (hp, wp)
-    pb = ProgramBuilder()
     RELU = L.PP_RELU_LAST
 
     def convbn(x, conv, bn, *, stride=1, relu=RELU, **kw):
@@ -256,8 +261,17 @@ def build_dla34_program(sd: dict, hp: int, wp: int, keep=()) -> Program:
     feat = z[-1]
     h, w, _ = pb.dims(feat)
     assert (h, w) == (hp // DOWN_RATIO, wp // DOWN_RATIO)
+    return feat
+
+
+def build_dla34_program(sd: dict, hp: int, wp: int, keep=()) -> Program:
+    """hp, wp: network input size, multiples of 32.  keep: op names whose outputs keep a buffer of their own, found under that
+    name in Program.named (tests and profiles that read an intermediate map)"""
+    pb = ProgramBuilder()
+    feat = dla34_trunk(pb, sd, hp, wp)
+    h, w, _ = pb.dims(feat)
     for head, c in HEADS:
-        t = pb.conv(feat, sd[f"{head}.0.weight"], sd[f"{head}.0.bias"], pad=1, relu=RELU, name=f"{head}.0")
+        t = pb.conv(feat, sd[f"{head}.0.weight"], sd[f"{head}.0.bias"], pad=1, relu=L.PP_RELU_LAST, name=f"{head}.0")
         o = pb.buf(h, w, c, name=head)
         pb.conv(t, sd[f"{head}.2.weight"], sd[f"{head}.2.bias"], out=o, name=f"{head}.2")
     for name in keep:

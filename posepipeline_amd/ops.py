@@ -201,6 +201,50 @@ def fairmot_decode(ctx: L.Context, hm_dev: int, wh_dev: int, reg_dev: int, id_de
     return dets, feats, inds
 
 
+# ---- TraDeS (trades.hip, fairmot.hip) ------------------------------------------------------------------------------------------------
+def trades_cva(ctx: L.Context, emb_cur, emb_prev, want_soft=False):
+    """pp_trades_cva on host arrays: emb_cur, emb_prev [n][hc][wc][128] float32 -> (tracking_offset [n][2 hc][2 wc][2] with channel 0 =
+    off_w and 1 = off_h, soft_h [n][P][hc] or None, soft_w [n][P][wc] or None)"""
+    emb_cur, emb_prev = (np.ascontiguousarray(e, np.float32) for e in (emb_cur, emb_prev))
+    n, hc, wc, dim = emb_cur.shape
+    assert emb_prev.shape == emb_cur.shape
+    off = np.empty((n, 2 * hc, 2 * wc, 2), np.float32)
+    sh = np.empty((n, hc * wc, hc), np.float32) if want_soft else None
+    sw = np.empty((n, hc * wc, wc), np.float32) if want_soft else None
+    L.check(ctx.lib.pp_trades_cva(ctx.handle, L.ptr(emb_cur), L.ptr(emb_prev), n, hc, wc, dim, L.ptr(off), L.ptr(sh), L.ptr(sw), L.PP_MEM_HOST),
+            "pp_trades_cva")
+    return off, sh, sw
+
+
+def trades_cva_dev(ctx: L.Context, cur_dev: int, prev_dev: int, n: int, hc: int, wc: int, off_dev: int, dim: int = 128):
+    """pp_trades_cva on device pointers; queued on the context's stream"""
+    L.check(ctx.lib.pp_trades_cva(ctx.handle, C.c_void_p(cur_dev), C.c_void_p(prev_dev), n, hc, wc, dim, C.c_void_p(off_dev), None, None,
+                                  L.PP_MEM_DEVICE), "pp_trades_cva")
+
+
+def trades_render_prehm(ctx: L.Context, boxes, hp: int, wp: int, out_dev=None):
+    """pp_trades_render_prehm: boxes int [m][3] = (cx, cy, radius) in network-input pixels -> the pooled map [hp / 4][wp / 4] float32 (numpy),
+    or written to the device address out_dev (returns None)"""
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(-1, 3)
+    if out_dev is not None:
+        L.check(ctx.lib.pp_trades_render_prehm(ctx.handle, L.ptr(boxes) if len(boxes) else None, len(boxes), hp, wp, C.c_void_p(int(out_dev)),
+                                               L.PP_MEM_DEVICE), "pp_trades_render_prehm")
+        return None
+    out = np.empty((hp // 4, wp // 4), np.float32)
+    L.check(ctx.lib.pp_trades_render_prehm(ctx.handle, L.ptr(boxes) if len(boxes) else None, len(boxes), hp, wp, L.ptr(out), L.PP_MEM_HOST),
+            "pp_trades_render_prehm")
+    return out
+
+
+def trades_decode(ctx: L.Context, hm_dev: int, reg_dev: int, ltrb_dev: int, trk_dev: int, n: int, h: int, w: int, K: int):
+    """pp_trades_decode on device head maps (NHWC) -> (dets [n][K][9] float32 = ct 2, bbox 4, tracking 2, score; inds [n][K] int32)"""
+    dets = np.zeros((n, K, 9), np.float32)
+    inds = np.zeros((n, K), np.int32)
+    L.check(ctx.lib.pp_trades_decode(ctx.handle, C.c_void_p(hm_dev), C.c_void_p(reg_dev), C.c_void_p(ltrb_dev), C.c_void_p(trk_dev), n, h, w, K,
+                                     L.ptr(dets), L.ptr(inds), L.PP_MEM_HOST), "pp_trades_decode")
+    return dets, inds
+
+
 # ---- SMPL stage: VIBE (crop_affine.hip, gru.hip, smpl.hip) ---------------------------------------------------------------------------
 def warp_affine_normalize_each(ctx: L.Context, frames, frame_idx, matrices, out_wh=(224, 224), lut=None, chan_map=(0, 1, 2),
                                want_crop_u8=False, out_dev=None, frames_dev_shape=None):

@@ -184,6 +184,9 @@ class TrackingBbox(dj.Computed):  # pipeline.py:508-513
         elif name == "FairMOT":            # pipeline.py:549-553
             from .wrappers.fairmot import fairmot_bounding_boxes
             tracks = fairmot_bounding_boxes(video)
+        elif name == "TraDeS":             # pipeline.py:561-565
+            from .wrappers.trades import trades_bounding_boxes
+            tracks = trades_bounding_boxes(video)
         else:
             raise Exception(f"Unsupported tracking method: {key['tracking_method']}")
         key["tracks"] = tracks

@@ -380,6 +380,32 @@ class ProgramBuilder:
                               flops=2.0 * 4 * c * h * w * stride * stride))
         return out
 
+    # ---- TraDeS' program B (PP_OP_SUB_CAT / PP_OP_BCAST_MUL / PP_OP_BLEND2; include/posepipe_hip.h) -------------------------------
+    def _ew_op(self, type_, x, out, *, res1=-1, in2=-1, in3=-1, name="op") -> int:
+        self.vops.append(dict(type=type_, in_=x, out=out, res1=res1, res2=-1, cin=self.dims(x)[2], cout=self.dims(out)[2], kh=1, kw=1,
+                              stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
+                              out_c_off=0, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, in2=in2, in3=in3, up2_log2=0, up3_log2=0,
+                              flops=0.0))
+        return out
+
+    def sub_cat(self, a, b, lead, name="sub_cat") -> int:
+        """[h][w][4 + c]: channels [0, c2) = lead ([h][w][c2 <= 4]), [c2, 4) zeros, [4, 4 + c) = a - b"""
+        h, w, c = self.dims(a)
+        assert self.dims(b) == (h, w, c) and c % 4 == 0 and self.dims(lead)[:2] == (h, w) and 1 <= self.dims(lead)[2] <= 4
+        return self._ew_op(L.PP_OP_SUB_CAT, a, self.buf(h, w, c + 4), res1=b, in2=lead, name=name)
+
+    def bcast_mul(self, x, gate, name="bcast_mul") -> int:
+        """gate [h][w][1] * x [h][w][c]"""
+        h, w, c = self.dims(x)
+        assert c % 4 == 0 and self.dims(gate) == (h, w, 1)
+        return self._ew_op(L.PP_OP_BCAST_MUL, x, self.buf(h, w, c), in2=gate, name=name)
+
+    def blend2(self, x0, x1, logit0, logit1, name="blend2") -> int:
+        """a0 x0 + a1 x1 with (a0, a1) = softmax(logit0, logit1) per pixel; logits [h][w][1]"""
+        h, w, c = self.dims(x0)
+        assert c % 4 == 0 and self.dims(x1) == (h, w, c) and self.dims(logit0) == (h, w, 1) and self.dims(logit1) == (h, w, 1)
+        return self._ew_op(L.PP_OP_BLEND2, x0, self.buf(h, w, c), res1=x1, in2=logit0, in3=logit1, name=name)
+
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
         a 4-term gather (PP_OP_DECONV_BF16).  weight: torch ConvTranspose2d layout [cin][cout][4][4], BN already folded."""

@@ -752,3 +752,54 @@ class JDETracker:
         self.tracked = [t for i, t in enumerate(self.tracked) if i not in dupa]
         self.lost = [t for i, t in enumerate(self.lost) if i not in dupb]
         return [(t.track_id, t.tlwh, t.score) for t in self.tracked if t.is_activated]
+
+
+# ---- TraDeS / CenterTrack tracker (wrappers/trades.py) -------------------------------------------------------------------------------
+class TradesTracker:
+    """CenterTrack's `Tracker.step` with the reference wrapper's settings (max_age = -1, hungarian = False, public_det = False, one
+    class), on the host after the detections are decoded.  For detections d (in score order) and tracks t: dist = ||t.ct - (d.ct +
+    d.tracking)||^2 in float32; a pair is invalid (+ 1e18) when dist > area(t.bbox) or dist > area(d.bbox); greedy assignment: each
+    detection in turn takes its argmin over the tracks, accepted if < 1e16, and that track's column is then blocked.  A matched
+    detection inherits the track's id, an unmatched one with score > new_thresh gets the next id (ids start at 1 in every instance),
+    unmatched tracks are dropped.  The returned list (matched first, then new, each in detection order) is the next frame's tracks.
+    The first frame goes through the same step with no tracks.  Restated from memory of the published code: UNPINNED."""
+
+    def __init__(self, new_thresh=0.5):
+        self.new_thresh = new_thresh
+        self.id_count = 0
+        self.tracks: list = []
+
+    @staticmethod
+    def _area(items):
+        return np.array([(t["bbox"][2] - t["bbox"][0]) * (t["bbox"][3] - t["bbox"][1]) for t in items], np.float32)
+
+    def step(self, results):
+        """results: dicts with "score", "ct" [2], "tracking" [2], "bbox" [4] (source pixels), score descending -> the same dicts with
+        "tracking_id", "age" and "active" added"""
+        n, m = len(results), len(self.tracks)
+        dets = np.array([np.asarray(d["ct"], np.float32) + np.asarray(d["tracking"], np.float32) for d in results], np.float32).reshape(n, 2)
+        tracks = np.array([t["ct"] for t in self.tracks], np.float32).reshape(m, 2)
+        dist = ((tracks.reshape(1, m, 2) - dets.reshape(n, 1, 2)) ** 2).sum(axis=2)
+        invalid = (dist > self._area(self.tracks).reshape(1, m)) | (dist > self._area(results).reshape(n, 1))
+        dist = dist + invalid * 1e18
+        matches = []
+        if m > 0:
+            for i in range(n):
+                j = int(dist[i].argmin())
+                if dist[i, j] < 1e16:
+                    dist[:, j] = 1e18
+                    matches.append((i, j))
+        ret = []
+        for i, j in matches:
+            d = results[i]
+            d["tracking_id"], d["age"], d["active"] = self.tracks[j]["tracking_id"], 1, self.tracks[j]["active"] + 1
+            ret.append(d)
+        taken = {i for i, _ in matches}
+        for i in range(n):
+            d = results[i]
+            if i not in taken and d["score"] > self.new_thresh:
+                self.id_count += 1
+                d["tracking_id"], d["age"], d["active"] = self.id_count, 1, 1
+                ret.append(d)
+        self.tracks = ret
+        return ret
