@@ -893,6 +893,37 @@ int pp_trades_render_prehm(pp_ctx* ctx, const int32_t* boxes, int n_boxes, int h
 int pp_trades_decode(pp_ctx* ctx, const float* hm, const float* reg, const float* ltrb, const float* tracking, int n, int h, int w,
                      int K, float* dets, int32_t* inds, int mem);
 
+/* ---- GAST-Net lifting (gastnet.hip; models/gastnet.py, wrappers/gastnet.py) --------------------------------------------------------
+ * The two ops of GAST-Net's graph-attention blocks (LiftingMethodLookup row 0 "GastNet", pose_pipeline/wrappers/gastnet_lifting.py)
+ * besides convolutions.  GAST-Net is not vendored: UNPINNED restatements; numpy / torch twins in tests/gastnet_ref.py.
+ * Activations are [17 joints][w time steps][channels] per sample: H is the joint axis, and both ops mix over it within one time step.
+ * Float32 on the vector ALU, the same kernels in exact and split nets.  Added op types over existing pp_op fields only: sizeof(pp_op)
+ * is unchanged and PP_ABI_VERSION stays 10.  Every field not named keeps its neutral value.
+ *
+ * PP_OP_GRAPH_MIX: channel-wise graph convolution (SemCHGraphConv), kh = g graphs (1 .. 4) in one pass.
+ *   in [17][w][cin], cin = 2 cout: per graph q the channels [2 q c, 2 q c + c) = h0 (the self term), [2 q c + c, 2 q c + 2 c) = h1 (the
+ *   neighbour term), c = cout / g, c % 4 == 0 (a 1x1 PP_OP_CONV writes it).  out [17][w][>= out_c_off + cout]: graph q fills the
+ *   channels [out_c_off + q c, out_c_off + (q + 1) c), the others are untouched.
+ *   w_off: A[g][17][17][c], A[q][j][i][ch] = the weight of source joint i in output joint j for channel ch (ch fastest; zeros off the
+ *   graph's mask); b_off: bias[g][c], then nb[g][17]: nb[q][j] = the float whose integer value has bit i set when (j, i) is in the
+ *   mask of graph q (the neighbour list, built on the host: it says which terms EXIST, whatever the value of A there).
+ *     out[j][t][q c + ch] = act((sum over the i of nb[q][j], ascending, of A[q][j][i][ch] * (i == j ? h0 : h1)[i][t][ch]) + bias[q][ch]):
+ *   ONE fmaf chain from 0 over the source joints, then one float32 add of the bias; terms outside the mask are skipped, not
+ *   multiplied by zero.  relu: PP_RELU_NONE / PP_RELU_LAST.  No atomics.
+ * PP_OP_JOINT_ATTN: per time step, multi-head attention over the 17 joints (MultiGlobalGraph), no scale.
+ *   in [17][w][3 * cout] = the qkv map in PP_OP_ATTENTION's channel order: channel s * cout + head * hd + d holds (q, k, v)[s] of head
+ *   `head`, hd = cin / heads; channels [cin, cout) of each third are padding and are not read.  out [17][w][>= out_c_off + cout]:
+ *   channels [out_c_off, out_c_off + cout).  cin = heads * hd (hd % 4 == 0, hd <= 128) <= cout % 4 == 0, stride = heads; no parameters.
+ *   Per sample, time step t and head, over the joints i, j:
+ *     s[i][j] = q_i . k_j (one fmaf chain over d from 0);  m_i = max_j s[i][j];  e[i][j] = exp(s[i][j] - m_i) (the difference rounded to
+ *     float32, exp EVALUATED IN DOUBLE AND ROUNDED ONCE);  sum_i = e[i][0] + e[i][1] + ... in joint order;  p[i][j] = e[i][j] / sum_i;
+ *     out_i = sum_j p[i][j] v_j, one fmaf chain over j = 0 .. 16 from 0.
+ *   Channels [out_c_off + cin, out_c_off + cout) of `out` are exact zeros.  No atomics.
+ * Neither op folds its output's per-sample maxima (pp_amax.h): where a fp16-form convolution reads what they wrote, the net takes the
+ * maxima in a pass of its own behind the op, as for PP_OP_ATTENTION. */
+#define PP_OP_GRAPH_MIX 21
+#define PP_OP_JOINT_ATTN 22
+
 #ifdef __cplusplus
 }
 #endif

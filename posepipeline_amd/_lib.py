@@ -23,6 +23,7 @@ PP_OP_DWCONV3X3, PP_OP_LAYERNORM, PP_OP_WINDOW_ATTN, PP_OP_GELU_ADD = 11, 12, 13
 PP_OP_ATTENTION = 15     # global float32 multi-head attention (poseformer.hip)
 PP_OP_DCN3X3, PP_OP_DWDECONV = 16, 17     # DCNv2 3x3 and the depthwise transposed convolution of DLA-34's head (fairmot.hip)
 PP_OP_SUB_CAT, PP_OP_BCAST_MUL, PP_OP_BLEND2 = 18, 19, 20     # the elementwise steps of TraDeS' program B (trades.hip)
+PP_OP_GRAPH_MIX, PP_OP_JOINT_ATTN = 21, 22     # GAST-Net's channel-wise graph convolution and joint attention (gastnet.hip)
 PP_RELU_NONE, PP_RELU_LAST, PP_RELU_FIRST = 0, 1, 2
 PP_ACT_LEAKY, PP_ACT_MISH, PP_ACT_ELU, PP_ACT_SWISH = 3, 4, 5, 6
 PP_ACT_GELU = 7          # PP_OP_DWCONV3X3 only

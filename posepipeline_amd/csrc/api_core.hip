@@ -655,6 +655,27 @@ static int net_check_op(const pp_net& net, const pp_op& op, int idx) {
             if (b >= 0)
                 PP_REQUIRE(net.bufs[b].h == bi.h && net.bufs[b].w == bi.w && b != op.out && (cat ? net.bufs[b].c >= 1 && net.bufs[b].c <= 4 : net.bufs[b].c == 1),
                            "op %d: in2 / in3 must be [h][w][1] maps (sub_cat: [h][w][1 .. 4]) other than out", idx);
+    } else if (op.type == PP_OP_GRAPH_MIX) {
+        const int g = op.kh, c = g > 0 ? op.cout / g : 0;
+        PP_REQUIRE(g > 0 && g <= 4 && op.cout > 0 && op.cout % g == 0 && (c & 3) == 0 && op.cin == 2 * op.cout && bi.c == op.cin,
+                   "op %d: graph_mix needs kh = graphs (1 .. 4), cout = graphs * c (c %% 4 == 0) and in [17][w][cin = 2 * cout]", idx);
+        PP_REQUIRE(bi.h == 17 && bo.h == 17 && bo.w == bi.w && (bo.c & 3) == 0 && op.out_c_off + op.cout <= bo.c && op.in != op.out,
+                   "op %d: graph_mix needs in [17][w][cin] and a distinct out [17][w][>= out_c_off + cout], channels %% 4 == 0", idx);
+        PP_REQUIRE(op.relu == PP_RELU_NONE || op.relu == PP_RELU_LAST, "op %d: graph_mix supports PP_RELU_NONE / PP_RELU_LAST", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.in_c_off == 0 && op.up_log2 == 0, "op %d: graph_mix has no residuals, input slices or upsampling", idx);
+        PP_REQUIRE(op.w_off >= 0 && (op.w_off % 4) == 0 && (size_t)op.w_off + (size_t)289 * op.cout <= net.n_weights && op.b_off >= 0 &&
+                       (op.b_off % 4) == 0 && (size_t)op.b_off + (size_t)op.cout + (size_t)17 * g <= net.n_weights,
+                   "op %d: graph_mix parameters out of blob", idx);
+    } else if (op.type == PP_OP_JOINT_ATTN) {
+        PP_REQUIRE(op.stride > 0 && op.cin > 0 && op.cin % op.stride == 0 && op.cin <= op.cout && (op.cout & 3) == 0 &&
+                       ((op.cin / op.stride) & 3) == 0 && op.cin / op.stride <= pp_joint_attn_max_head_dim(),
+                   "op %d: joint_attn needs cin = heads (stride) * head dim (a multiple of 4, at most %d) <= cout, cout %% 4 == 0", idx,
+                   pp_joint_attn_max_head_dim());
+        PP_REQUIRE(bi.h == 17 && bi.c == 3 * op.cout && bo.h == 17 && bo.w == bi.w && (bo.c & 3) == 0 && op.out_c_off + op.cout <= bo.c &&
+                       op.in != op.out,
+                   "op %d: joint_attn needs in [17][w][3 * cout] (the qkv map) and a distinct out [17][w][>= out_c_off + cout]", idx);
+        PP_REQUIRE(op.res1 < 0 && op.res2 < 0 && !op.out_nchw && op.in_c_off == 0 && op.up_log2 == 0 && op.relu == PP_RELU_NONE,
+                   "op %d: joint_attn has no residuals, input slices, upsampling or activation", idx);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         PP_REQUIRE(op.cin == op.cout && bi.c == op.cin && bo.c == op.cin && bi.h == bo.h && bi.w == bo.w && op.in != op.out,
                    "op %d: vit encoder needs distinct in / out buffers of [h][w][dim]", idx);
@@ -780,6 +801,12 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
     } else if (op.type == PP_OP_BLEND2) {
         return pp_launch_blend2(net->buf_ptr(op.in), net->buf_ptr(op.res1), net->buf_ptr(op.in2), net->buf_ptr(op.in3), net->buf_ptr(op.out),
                                 (size_t)batch * bi.h * bi.w, op.cin, s);
+    } else if (op.type == PP_OP_GRAPH_MIX) {
+        return pp_launch_graph_mix(net->buf_ptr(op.in), net->weights + op.w_off, net->weights + op.b_off, net->buf_ptr(op.out), batch, bi.h,
+                                   bi.w, op.kh, op.cout / op.kh, bo.c, op.out_c_off, op.relu == PP_RELU_LAST, s);
+    } else if (op.type == PP_OP_JOINT_ATTN) {
+        return pp_launch_joint_attn(net->buf_ptr(op.in), net->buf_ptr(op.out), batch, bi.h, bi.w, op.stride, op.cin, op.cout, bo.c,
+                                    op.out_c_off, s);
     } else if (op.type == PP_OP_VIT_ENCODER) {
         pp_vit_encoder* enc = net->vits[&op - net->ops.data()];
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);

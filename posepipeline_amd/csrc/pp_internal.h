@@ -270,6 +270,14 @@ int pp_launch_dwdeconv(const float* x, const float* wgt, const float* res, float
 int pp_launch_sub_cat(const float* a, const float* b, const float* lead, float* y, size_t pixels, int c, int c2, hipStream_t stream);
 int pp_launch_bcast_mul(const float* x, const float* g, float* y, size_t pixels, int c, hipStream_t stream);
 int pp_launch_blend2(const float* x0, const float* x1, const float* l0, const float* l1, float* y, size_t pixels, int c, hipStream_t stream);
+// ---- PP_OP_GRAPH_MIX / PP_OP_JOINT_ATTN (gastnet.hip; field by field in posepipe_hip.h) ----------------------------------------
+// x [n][17][w][2 g c], amat [g][17][17][c], bias_nb = bias [g][c] then mask bits [g][17] -> y [n][17][w][y_coff + g c of y_stride]
+int pp_launch_graph_mix(const float* x, const float* amat, const float* bias_nb, float* y, int n, int h, int w, int g, int c,
+                        int y_stride, int y_coff, int relu, hipStream_t stream);
+// qkv [n][17][w][3 * c_buf] -> out [n][17][w][y_coff + c_buf of y_stride]
+int pp_launch_joint_attn(const float* qkv, float* out, int n, int h, int w, int heads, int c_real, int c_buf, int y_stride, int y_coff,
+                         hipStream_t stream);
+int pp_joint_attn_max_head_dim();
 // encoder behind PP_OP_VIT_ENCODER; `params` is a DEVICE pointer into the program's fp32 weight blob
 struct pp_vit_encoder;
 size_t pp_vit_param_floats(int tokens, int dim, int depth, int hidden);

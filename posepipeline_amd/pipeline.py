@@ -411,6 +411,11 @@ class LiftingPerson(dj.Computed):  # pipeline.py:1252-1257
         if name == "VideoPose3D":
             from .wrappers.videopose3d import process_videopose3d
             results = process_videopose3d(key)
+        elif name == "GastNet":  # pipeline.py:1265-1269; as there, only where the model is installed (the reference: GAST_PATH)
+            from .wrappers import gastnet
+            if not os.path.exists(gastnet.checkpoint_path()):
+                raise Exception(f"Method not implemented {key}: the GAST-Net checkpoint {gastnet.checkpoint_path()} is not installed")
+            results = gastnet.process_gastnet(key)
         else:
             raise Exception(f"Method not implemented {key}")
         key.update(results)

@@ -406,6 +406,55 @@ class ProgramBuilder:
         assert c % 4 == 0 and self.dims(x1) == (h, w, c) and self.dims(logit0) == (h, w, 1) and self.dims(logit1) == (h, w, 1)
         return self._ew_op(L.PP_OP_BLEND2, x0, self.buf(h, w, c), res1=x1, in2=logit0, in3=logit1, name=name)
 
+    # ---- GAST-Net's graph-attention blocks (PP_OP_GRAPH_MIX / PP_OP_JOINT_ATTN; include/posepipe_hip.h) ------------------------------
+    def graph_mix(self, x, mats, biases, masks, *, relu=L.PP_RELU_NONE, out=None, out_c_off=0, name="graph_mix") -> int:
+        """Channel-wise graph convolution of g graphs in one pass.  x: [17][w][2 g c], per graph h0 then h1 (a 1x1 convolution writes
+        it).  mats: g arrays A[17][17][c] (output joint, source joint, channel); biases: g arrays [c]; masks: g boolean [17][17], the
+        terms that exist -- A must be zero elsewhere.  Returns [17][w][g c], or writes that slice of `out` at out_c_off."""
+        h, w, cin = self.dims(x)
+        g = len(mats)
+        mats = [np.asarray(a, np.float32) for a in mats]
+        c = mats[0].shape[2]
+        assert h == 17 and 1 <= g <= 4 and c % 4 == 0 and cin == 2 * g * c and len(biases) == g and len(masks) == g, (h, g, c, cin)
+        bits = []
+        for a, m in zip(mats, masks):
+            m = np.asarray(m, bool)
+            assert a.shape == (17, 17, c) and m.shape == (17, 17) and not a[~m].any(), (a.shape, m.shape)
+            bits.append([sum(1 << i for i in range(17) if m[j, i]) for j in range(17)])
+        if out is None:
+            assert out_c_off == 0
+            out = self.buf(h, w, g * c)
+        else:
+            oh, ow, oc = self.dims(out)
+            assert (oh, ow) == (h, w) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + g * c <= oc, (self.dims(out), h, w, g * c, out_c_off)
+        w_off = self._add_blob(np.stack(mats))
+        b_off = self._add_blob(np.concatenate([np.stack([np.asarray(b, np.float32).reshape(c) for b in biases]).reshape(-1),
+                                               np.asarray(bits, np.float32).reshape(-1)]))
+        nnz = sum(int(np.asarray(m, bool).sum()) for m in masks)
+        self.vops.append(dict(type=L.PP_OP_GRAPH_MIX, in_=x, out=out, res1=-1, res2=-1, cin=cin, cout=g * c, kh=g, kw=1, stride=1, pad_h=0,
+                              pad_w=0, dil_h=1, dil_w=1, relu=relu, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
+                              out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, flops=2.0 * w * c * nnz))
+        return out
+
+    def joint_attention(self, qkv, *, c_real, heads, out=None, out_c_off=0, name="joint_attn") -> int:
+        """Per time step, multi-head attention over the 17 joints, no scale (PP_OP_JOINT_ATTN), on a qkv map [17][w][3 * c_buf] in
+        PP_OP_ATTENTION's channel order.  Returns [17][w][c_buf] with channels >= c_real exact zeros, or writes that slice of `out`."""
+        h, w, c3 = self.dims(qkv)
+        c_buf = c3 // 3
+        assert h == 17 and c3 == 3 * c_buf and c_buf % 4 == 0 and c_real <= c_buf and c_real % heads == 0, (h, c3, c_real, heads)
+        hd = c_real // heads
+        assert hd % 4 == 0 and hd <= 128, hd
+        if out is None:
+            assert out_c_off == 0
+            out = self.buf(h, w, c_buf)
+        else:
+            oh, ow, oc = self.dims(out)
+            assert (oh, ow) == (h, w) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + c_buf <= oc, (self.dims(out), h, w, c_buf, out_c_off)
+        self.vops.append(dict(type=L.PP_OP_JOINT_ATTN, in_=qkv, out=out, res1=-1, res2=-1, cin=c_real, cout=c_buf, kh=1, kw=1, stride=heads,
+                              pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
+                              out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, flops=2.0 * 2 * w * 17 * 17 * c_real))
+        return out
+
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
         a 4-term gather (PP_OP_DECONV_BF16).  weight: torch ConvTranspose2d layout [cin][cout][4][4], BN already folded."""

@@ -11,8 +11,9 @@ The DEFAULTS are the reference's own (utils/standard_pipelines.py:12,58-59,112-1
   * top_down_method_name "MMpose" -- NOT a row of TopDownMethodLookup (the row is spelled "MMPose"), so a call that relies on
     the default fails in the lookup's fetch1, exactly like the reference; callers pass "MMPose" / "MMPoseHalpe" / ...
     (scripts/process_h36m.py does);
-  * lifting_method_name "GastNet" -- a lookup row whose wrapper is outside the hot path:
-    LiftingPerson.make raises for it; callers of the hot path pass "VideoPose3D";
+  * lifting_method_name "GastNet" -- lifting_method 0, built here (wrappers/gastnet.py, models/gastnet.py).  As in the reference, which
+    needs GAST_PATH, it runs only where the model is installed: without `gastnet/27_frame_model.bin` under MODEL_DATA_DIR
+    LiftingPerson.make raises "Method not implemented" naming the missing file; "VideoPose3D" is the other built row;
   * smpl_method_name "PIXIE" -- a lookup row that is not built: SMPLPerson.make raises "not implemented"; callers pass "VIBE".
 A method name that is not in its lookup table raises from fetch1 (no silent substitution).  `BestDetectedFrames` is populated
 where the reference populates it (:100, :162); the OpenPose branch (:95-97, SURVEY.md section 2, out of scope) is not part of
