@@ -306,6 +306,16 @@ int pp_net_profile(pp_net* net, int batch, float* ms_per_op);
  * (conv_igemm*.hip), 2 = bf16-split kernel (conv_split.hip).  kinds: n_ops ints.  (bench.py prices the two families
  * against their own peaks.) */
 int pp_net_conv_kinds(pp_net* net, int* kinds);
+/* Folded projection shortcuts (fp16-form nets only; fixed at creation).  A 1x1 convolution A (any stride; no activation, no
+ * residuals) whose output is read exactly once, as the plain res1 of a 1x1 / stride-1 convolution B that runs on the product kernel,
+ * is not launched: B evaluates act(W_B h + W_A x + (b_B + b_A)) as ONE product over the concatenated input channels, under one
+ * activation scale per sample (from the larger of the two inputs' maxima) and one weight scale per output channel (over both
+ * weights).  A's output buffer is then never written.  The op numbering is the caller's: into[i] (n_ops ints) = the op that carries
+ * op i, or -1 for an op that is launched; pp_net_profile reports 0 ms for a folded op, and pp_net_conv_kinds 2 (its product runs on
+ * the split kernel).  POSEPIPE_SPLIT_FOLD=0 (read when a net is created) folds nothing; POSEPIPE_SPLIT_FOLD_OFF lists layer classes
+ * that keep their two launches, as comma-separated "<B's cin>+<A's cin>" or "<B's cin>+<A's cin>@<out h>x<out w>" (setting it replaces
+ * the built-in list).  Exact and bf16-form nets are never rewritten.  Added function only: PP_ABI_VERSION stays 10. */
+int pp_net_folded_into(pp_net* net, int* into);
 
 /* Tile configuration of the convolution kernel for all later launches of this process: ct = output-channel tile / 16
  * (1..4), pt = pixel tile / 64 (1, 2); 0 = automatic (posepipeline_amd/conv_tuning.txt, then the built-in heuristic).

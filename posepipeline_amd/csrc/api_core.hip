@@ -275,6 +275,20 @@ struct pp_net {
     // contiguous range (slot_owner = the first op that raises the slot).
     unsigned* amax = nullptr;
     std::vector<int> op_x_slot, op_y_slot, op_post_slot, slot_owner;
+    std::vector<int> op_x2_slot;                 // ... of the second input of an op that carries a folded shortcut (fold_src)
+    // projection shortcuts folded into the product they were added to (net_fold_shortcuts; fp16-form nets only).  The op list keeps the
+    // caller's numbering: the shortcut op stays in it and is never launched (fold_into[i] = the op that carries it), and the carrying
+    // op reads the shortcut's INPUT as a second K segment instead of the shortcut's output as res1 (fold_src[i] = the shortcut op)
+    std::vector<int> fold_into, fold_src;
+    bool folded(int i) const { return !fold_into.empty() && fold_into[i] >= 0; }
+    int carries(int i) const { return fold_src.empty() ? -1 : fold_src[i]; }
+    // the buffers op i reads, as executed: {in, res1, res2, in2, in3}
+    void reads(int i, int (&r)[5]) const {
+        const pp_op& op = ops[i];
+        r[0] = op.in; r[1] = op.res1; r[2] = op.res2; r[3] = op.in2; r[4] = op.in3;
+        if (folded(i)) r[0] = r[1] = r[2] = r[3] = r[4] = -1;
+        else if (carries(i) >= 0) r[1] = ops[carries(i)].in;
+    }
     std::vector<int> slot_first, slot_last;      // tracked slots: first / last op that raises them (-1: nobody reads the maxima)
     struct ExtAmax { int buf, slot, first_reader, last_reader; bool provided; };
     std::vector<ExtAmax> ext;      // tensors from outside the program that fp16-form convolutions read
@@ -303,6 +317,7 @@ struct pp_net {
 
 static ConvArgs net_conv_args(pp_net* net, const pp_op& op, int batch);
 static int net_make_lanes(pp_net* net, int n_lanes);
+static void net_fold_shortcuts(pp_net* net);
 
 // which tensors the fp16-form convolutions read, who produces them and who therefore tracks their maxima (see pp_net::amax)
 static void net_plan_amax(pp_net* net) {
@@ -310,10 +325,13 @@ static void net_plan_amax(pp_net* net) {
     net->op_x_slot.assign(n, -1);
     net->op_y_slot.assign(n, -1);
     net->op_post_slot.assign(n, -1);
+    net->op_x2_slot.assign(n, -1);
     net->slot_owner.clear();
     net->ext.clear();
     if (net->numerics != PP_NET_NUMERICS_SPLIT || !net->split_f16) return;
-    auto is_h = [&](int i) { return net->ops[i].type == PP_OP_CONV && net->split_plan[i].kernel != SPLIT_NONE; };
+    auto is_h = [&](int i) { return !net->folded(i) && net->ops[i].type == PP_OP_CONV && net->split_plan[i].kernel != SPLIT_NONE; };
+    // the k-th tensor op i reads in the fp16 form: its input, and the input of the shortcut folded into it (-1: none)
+    auto h_in = [&](int i, int k) { return k == 0 ? net->ops[i].in : net->carries(i) >= 0 ? net->ops[net->carries(i)].in : -1; };
     // producers with a fused maximum: convolutions (pp_conv_tracks_amax), PP_OP_UPSAMPLE_ADD and PP_OP_BILINEAR_ADD
     auto tracks = [&](int i) {
         const pp_op& op = net->ops[i];
@@ -327,17 +345,20 @@ static void net_plan_amax(pp_net* net) {
         std::vector<char> written(nb, 0);
         for (int i = 0; i < n; ++i) {
             const pp_op& op = net->ops[i];
-            if (is_h(i) && !written[op.in]) {
+            if (net->folded(i)) continue;             // (never launched: writes nothing)
+            for (int k = 0; k < 2; ++k) {
+                const int b = h_in(i, k);
+                if (!is_h(i) || b < 0 || written[b]) continue;
                 pp_net::ExtAmax* e = nullptr;
                 for (auto& x : net->ext)
-                    if (x.buf == op.in) e = &x;
+                    if (x.buf == b) e = &x;
                 if (!e) {
-                    net->ext.push_back({op.in, (int)net->slot_owner.size(), i, i, false});
+                    net->ext.push_back({b, (int)net->slot_owner.size(), i, i, false});
                     net->slot_owner.push_back(-1);    // (never part of the zeroed range: handled per run, below)
                     e = &net->ext.back();
                 }
                 e->last_reader = i;
-                net->op_x_slot[i] = e->slot;
+                (k ? net->op_x2_slot : net->op_x_slot)[i] = e->slot;
             }
             written[op.out] = 1;
         }
@@ -346,14 +367,20 @@ static void net_plan_amax(pp_net* net) {
     std::vector<Tensor> tensors;
     std::vector<int> cur(nb, -1);                 // tensor currently held by buffer b (-1: written outside the program)
     std::vector<char> read_since(nb, 1);
-    std::vector<std::pair<int, int>> readers;     // (H conv, tensor)
+    struct Reader { int op, tensor, k; };
+    std::vector<Reader> readers;                  // (H conv, tensor, which of its inputs)
     for (int i = 0; i < n; ++i) {
         const pp_op& op = net->ops[i];
-        if (is_h(i) && cur[op.in] >= 0) {
-            tensors[cur[op.in]].wanted = true;
-            readers.push_back({i, cur[op.in]});
+        if (net->folded(i)) continue;
+        for (int k = 0; k < 2; ++k) {
+            const int b = h_in(i, k);
+            if (!is_h(i) || b < 0 || cur[b] < 0) continue;
+            tensors[cur[b]].wanted = true;
+            readers.push_back({i, cur[b], k});
         }
-        for (int b : {op.in, op.res1, op.res2, op.in2, op.in3})
+        int rd[5];
+        net->reads(i, rd);
+        for (int b : rd)
             if (b >= 0) read_since[b] = 1;
         // a write after a read (or the first write) starts a new tensor; writes without a read in between fill the same one (the
         // channel slices of a concatenation)
@@ -388,7 +415,7 @@ static void net_plan_amax(pp_net* net) {
         else
             net->op_post_slot[t.producers.back()] = t.slot;
     }
-    for (const auto& r : readers) net->op_x_slot[r.first] = tensors[r.second].slot;
+    for (const auto& r : readers) (r.k ? net->op_x2_slot : net->op_x_slot)[r.op] = tensors[r.tensor].slot;
 }
 
 // ahead of ops [first, last) on `s`: zero the maxima they raise, and take the maxima of the outside tensors they read
@@ -432,11 +459,14 @@ static void net_plan_lanes(pp_net* net, int n_lanes) {
     std::vector<int> lane_tail(n_lanes, -1);
     for (int i = 0; i < n; ++i) {
         const pp_op& op = net->ops[i];
+        if (net->folded(i)) continue;                   // never launched: no lane, no dependencies, no event
+        int rd[5];
+        net->reads(i, rd);
         std::vector<int> deps;
         auto add = [&](int d) {
             if (d >= 0 && std::find(deps.begin(), deps.end(), d) == deps.end()) deps.push_back(d);
         };
-        for (int b : {op.in, op.res1, op.res2, op.in2, op.in3})
+        for (int b : rd)
             if (b >= 0) add(last_writer[b]);
         add(last_writer[op.out]);                       // WAW
         for (int r : readers[op.out]) add(r);           // WAR
@@ -459,7 +489,7 @@ static void net_plan_lanes(pp_net* net, int n_lanes) {
                 net->op_needs_event[d] = 1;
             }
         lane_tail[lane] = i;
-        for (int b : {op.in, op.res1, op.res2, op.in2, op.in3})
+        for (int b : rd)
             if (b >= 0 && b != op.out) readers[b].push_back(i);
         last_writer[op.out] = i;
         readers[op.out].clear();
@@ -723,6 +753,19 @@ static ConvArgs net_conv_args(pp_net* net, const pp_op& op, int batch) {
         a.x_amax = net->amax_slot(net->op_x_slot[idx]);
         a.y_amax = net->amax_slot(net->op_y_slot[idx]);
     }
+    if (net->carries((int)idx) >= 0) {      // the folded shortcut: a second K segment in place of res1
+        const pp_op& sc = net->ops[net->carries((int)idx)];
+        const pp_buf& bs = net->bufs[sc.in];
+        a.res1 = nullptr;
+        a.res1_H = a.res1_W = a.r1_pad = 0;
+        a.x2 = net->buf_ptr(sc.in);
+        a.w2 = net->weights + sc.w_off;
+        a.bias2 = net->weights + sc.b_off;
+        a.Cin2 = sc.cin; a.Hin2 = bs.h; a.Win2 = bs.w; a.stride2 = sc.stride; a.x2_pad = bs.pad;
+        if (idx < net->op_x2_slot.size()) a.x2_amax = net->amax_slot(net->op_x2_slot[idx]);
+        if (a.wsplit && net->split_plan[idx].cin2 > 0)      // b3 + bs, behind the fragments and scales of the split copy
+            a.bias = reinterpret_cast<const float*>(static_cast<const unsigned char*>(a.wsplit) + net->split_plan[idx].bias_off);
+    }
     return a;
 }
 
@@ -730,6 +773,7 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
 
 static int net_launch_op(pp_net* net, const pp_op& op, int batch, hipStream_t s) {
     const size_t idx = &op - net->ops.data();
+    if (net->folded((int)idx)) return PP_OK;      // a folded shortcut: computed inside the op that carries it
     int rc = net_launch_op_body(net, op, batch, s);
     if (rc == PP_OK && net->amax && net->op_post_slot[idx] >= 0)
         rc = pp_launch_amax(net->buf_ptr(op.out), batch, net->buf_elems[op.out], net->amax_slot(net->op_post_slot[idx]), s);
@@ -812,6 +856,72 @@ static int net_launch_op_body(pp_net* net, const pp_op& op, int batch, hipStream
         return pp_vit_encoder_run(enc, net->buf_ptr(op.in), net->buf_ptr(op.out), batch, s);
     }
     return PP_ERR_UNSUPPORTED;
+}
+
+// layer classes whose shortcut is NOT folded: "<B's cin>+<A's cin>" or "...@<out h>x<out w>", comma-separated (pp_net_folded_into).
+// The built-in list holds the classes that measured no faster folded (DESIGN_LOG.md, "Folded projection shortcuts")
+static const char* const kFoldOffBuiltin = "";
+static bool fold_class_on(int cin_b, int cin_a, int h, int w) {
+    const char* env = getenv("POSEPIPE_SPLIT_FOLD_OFF");
+    const std::string list = std::string(",") + (env ? env : kFoldOffBuiltin) + ",";
+    char key[64];
+    snprintf(key, sizeof(key), ",%d+%d,", cin_b, cin_a);
+    if (list.find(key) != std::string::npos) return false;
+    snprintf(key, sizeof(key), ",%d+%d@%dx%d,", cin_b, cin_a, h, w);
+    return list.find(key) == std::string::npos;
+}
+
+// Projection shortcuts of ResNet-style bottlenecks: act(W3 h + b3 + (Ws x + bs)) as ONE product over the concatenated K (see
+// conv_split_gemm_kernel, SEG2) -- the shortcut tensor is neither written nor read back and its launch disappears.  Pattern:
+//   A: 1x1 convolution (any stride, no padding), no activation, no residuals, a plain NHWC tensor of its own;
+//   A's output is read by exactly one op B before the buffer is overwritten (or the program ends), only as B's res1 with
+//   res1_shift == 0, and nobody writes A's INPUT between A and B (B reads it in A's place);
+//   B: 1x1 / stride-1 convolution that the split plan puts on the product kernel in the fp16 form; same output geometry as A.
+// Runs after every op has its plan and before the maxima and lanes are planned: both see the dataflow as executed (pp_net::reads).
+static void net_fold_shortcuts(pp_net* net) {
+    const int n = (int)net->ops.size();
+    net->fold_into.assign(n, -1);
+    net->fold_src.assign(n, -1);
+    const char* env = getenv("POSEPIPE_SPLIT_FOLD");
+    if (net->numerics != PP_NET_NUMERICS_SPLIT || !net->split_f16 || (env && atoi(env) == 0)) return;
+    for (int ia = 0; ia < n; ++ia) {
+        const pp_op& A = net->ops[ia];
+        if (A.type != PP_OP_CONV || A.kh != 1 || A.kw != 1 || A.pad_h != 0 || A.pad_w != 0 || A.pad_end != 0 || A.stride < 1 ||
+            A.relu != PP_RELU_NONE || A.res1 >= 0 || A.res2 >= 0 || A.up_log2 != 0 || A.out_nchw || A.out_c_off != 0 || A.in == A.out ||
+            net->bufs[A.out].c != A.cout || net->bufs[A.out].pad != 0 || net->bufs[A.in].pad != 0 || A.cin % 16 != 0 || net->carries(ia) >= 0)
+            continue;
+        // the readers of A's tensor, and what happens to A's input meanwhile
+        int ib = -1, nread = 0;
+        bool ok = true;
+        for (int j = ia + 1; j < n && ok; ++j) {
+            const pp_op& o = net->ops[j];
+            int uses = 0;
+            for (int b : {o.in, o.res1, o.res2, o.in2, o.in3}) uses += b == A.out;
+            if (uses) {
+                ++nread;
+                ib = j;
+                ok = nread == 1 && uses == 1 && o.res1 == A.out;
+            }
+            if (o.out == A.out) break;                    // the buffer holds another tensor from here on
+            if (nread == 0 && o.out == A.in) ok = false;  // A's input changes before B would read it
+        }
+        if (!ok || nread != 1) continue;
+        const pp_op& B = net->ops[ib];
+        const pp_buf &ya = net->bufs[A.out], &yb = net->bufs[B.out];
+        if (B.type != PP_OP_CONV || B.kh != 1 || B.kw != 1 || B.stride != 1 || B.res1_shift != 0 || B.res1_off_w != 0 || B.up_log2 != 0 ||
+            B.cout != A.cout || yb.h != ya.h || yb.w != ya.w || B.out == A.in || net->carries(ib) >= 0 || net->folded(ib) ||
+            net->split_plan[ib].kernel != SPLIT_PRODUCT || !net->split_plan[ib].f16 || !fold_class_on(B.cin, A.cin, yb.h, yb.w))
+            continue;
+        net->fold_into[ia] = ib;
+        net->fold_src[ib] = ia;
+        const SplitPlan p = pp_conv_split_plan(net_conv_args(net, B, 1));
+        if (p.kernel != SPLIT_PRODUCT || p.cin2 != A.cin) {      // the product kernel does not take this pair: two launches, as before
+            net->fold_into[ia] = net->fold_src[ib] = -1;
+            continue;
+        }
+        net->split_plan[ib] = p;
+        net->split_plan[ia] = SplitPlan();
+    }
 }
 
 int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c) {
@@ -927,9 +1037,14 @@ int pp_net_create_ex(pp_ctx* ctx, const pp_op* ops, int n_ops, const pp_buf* buf
             if (net->ops[i].type != PP_OP_CONV) continue;
             SplitPlan p = pp_conv_split_plan(net_conv_args(net.get(), net->ops[i], 1));
             if (p.kernel == SPLIT_NONE) continue;
+            net->split_plan[i] = p;
+        }
+        net_fold_shortcuts(net.get());
+        for (int i = 0; i < n_ops; ++i) {
+            SplitPlan& p = net->split_plan[i];
+            if (p.kernel == SPLIT_NONE) continue;
             p.off = (long long)bytes;
             bytes += (p.bytes + 255) / 256 * 256;
-            net->split_plan[i] = p;
         }
         net_plan_amax(net.get());
         if (!net->slot_owner.empty()) {
@@ -942,7 +1057,9 @@ int pp_net_create_ex(pp_ctx* ctx, const pp_op* ops, int n_ops, const pp_buf* buf
             for (int i = 0; i < n_ops; ++i) {
                 const SplitPlan& p = net->split_plan[i];
                 if (p.kernel == SPLIT_NONE) continue;
-                int rc = pp_conv_split_weights(p, net_conv_args(net.get(), net->ops[i], 1), net->wsplit + p.off, ctx->stream);
+                ConvArgs ca = net_conv_args(net.get(), net->ops[i], 1);
+                ca.bias = net->weights + net->ops[i].b_off;      // (a folded op: its own bias -- the sum is made from it here)
+                int rc = pp_conv_split_weights(p, ca, net->wsplit + p.off, ctx->stream);
                 if (rc != PP_OK) return rc;
             }
         }
@@ -1008,8 +1125,16 @@ int pp_net_conv_kinds(pp_net* net, int* kinds) {
             kinds[i] = 0;
             continue;
         }
-        kinds[i] = net->split_plan[i].kernel != SPLIT_NONE ? 2 : 1;
+        // (a folded shortcut keeps kind 2: its product runs on the split kernel, inside the op that carries it -- so sums of a caller's
+        // per-op FLOPs by kind stay whole; pp_net_profile reports it with 0 ms and pp_net_folded_into names the carrying op)
+        kinds[i] = net->split_plan[i].kernel != SPLIT_NONE || net->folded((int)i) ? 2 : 1;
     }
+    return PP_OK;
+}
+
+int pp_net_folded_into(pp_net* net, int* into) {
+    PP_REQUIRE(net && into, "pp_net_folded_into: NULL argument");
+    for (size_t i = 0; i < net->ops.size(); ++i) into[i] = net->folded((int)i) ? net->fold_into[i] : -1;
     return PP_OK;
 }
 

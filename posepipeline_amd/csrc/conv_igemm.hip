@@ -727,8 +727,14 @@ int pp_launch_conv(const ConvArgs& a_in, const SplitPlan* plan, hipStream_t stre
         pp_set_error("conv: one input image of %zu bytes exceeds the 4 GiB buffer range", img_bytes);
         return PP_ERR_ARG;
     }
-    if ((size_t)a.N * img_bytes > max_bytes) {
-        const int per = (int)(max_bytes / img_bytes);
+    // (a folded shortcut's input, ConvArgs::x2, is addressed with 32-bit offsets as well: both inputs of a range stay under the limit)
+    const size_t img2_bytes = a.Cin2 > 0 ? (size_t)(a.Hin2 + a.x2_pad) * (a.Win2 + a.x2_pad) * a.Cin2 * sizeof(float) : 0;
+    if (img2_bytes > max_bytes) {
+        pp_set_error("conv: one input image of %zu bytes exceeds the 4 GiB buffer range", img2_bytes);
+        return PP_ERR_ARG;
+    }
+    if ((size_t)a.N * std::max(img_bytes, img2_bytes) > max_bytes) {
+        const int per = (int)(max_bytes / std::max(img_bytes, img2_bytes));
         const size_t y_img = (size_t)((a.Hout << a.up_log2) + a.y_pad) * ((a.Wout << a.up_log2) + a.y_pad) * (a.y_stride ? a.y_stride : a.Cout);
         const size_t r1_img = (size_t)(a.res1_H + a.r1_pad) * (a.res1_W + a.r1_pad) * a.Cout;
         const size_t r2_img = (size_t)((a.Hout << a.up_log2) + a.r2_pad) * ((a.Wout << a.up_log2) + a.r2_pad) * a.Cout;
@@ -741,6 +747,8 @@ int pp_launch_conv(const ConvArgs& a_in, const SplitPlan* plan, hipStream_t stre
             if (a.res1) p.res1 = a.res1 + (size_t)n0 * r1_img;
             if (a.res2) p.res2 = a.res2 + (size_t)n0 * r2_img;
             if (a.x_amax) p.x_amax = a.x_amax + n0;
+            if (a.x2) p.x2 = a.x2 + (size_t)n0 * (img2_bytes / sizeof(float));
+            if (a.x2_amax) p.x2_amax = a.x2_amax + n0;
             if (a.y_amax) p.y_amax = a.y_amax + n0;
             const int rc = pp_launch_conv(p, plan, stream);
             if (rc != PP_OK) return rc;

@@ -94,6 +94,12 @@ struct SplitArgs {
     const unsigned* x_amax;
     // any form: where to fold max |y| per sample of what this launch stores (null: the output feeds no fp16-form convolution)
     unsigned* y_amax;
+    // conv_split_gemm_kernel<.., H, SEG2>: the second K segment (a folded projection shortcut, ConvArgs::x2).  Stages [0, seg1) read x
+    // (Cin channels), stages [seg1, nchunks) read x2 (Cin2 channels at stride2 of an xp2_h x xp2_w map); the weight fragments of the
+    // two segments follow each other in stage order
+    const float* x2;
+    const unsigned* x2_amax;
+    int Cin2, stride2, xp2_h, xp2_w, seg1;
 #ifdef PP_SPLIT_TIMELINE
     unsigned long long* dbg;              // diagnosis builds only (tools/build_variant.sh tl -DPP_SPLIT_TIMELINE): 16 x u64 per workgroup
 #endif
@@ -1438,8 +1444,22 @@ __global__ __launch_bounds__(256) void split_weights48_kernel(const float* w, ui
 // order and shared by the waves along M), two LDS stages of 16 input channels, one barrier per stage (3072 matrix-pipe cycles).
 // WM x WN = 8 waves: one workgroup per CU; 4 waves (256 x 128 tile): two workgroups per CU, for layers with few 16-channel stages,
 // where one workgroup's start-up and epilogue hide under the other's K loop.
-template <int WM, int WN, bool H = false>
+//
+// SEG2 (fp16 form only): a projection shortcut folded into the product.  relu(W3 h + b3 + Ws x + bs) is ONE product over the
+// concatenated K = Cin + Cin2: stages [0, seg1) stream h (a.x), stages [seg1, nchunks) stream x (a.x2, read at its own stride) into the
+// same pixel ring, and the weight fragments of the two segments follow each other in stage order, so the K loop itself does not know
+// about segments -- only issue(c) picks the source.  Both segments add into the SAME float32 accumulators, so they share their scales:
+// sample n's activation scale follows max(amax_h[n], amax_x[n]) (no rescaling between the segments: the ratio of two scales can
+// overflow float32) and channel co's weight scale follows max(|W3[co, :]|, |Ws[co, :]|) (the concatenated weight is split as one).
+// Error: under a scale s with max |v| s in [2^14, 2^15), h0 = f16(v s) and h1 = f16(v s - h0) leave a residual of at most
+// max(2^-22 |v s|, 2^-25) (the second term's rounding; 2^-24 is the float16 subnormal spacing).  So an element down to 2^-17 of the
+// scale's maximum -- an operand ~10^5 smaller than its partner segment -- still carries its 22 bits; below that its absolute error
+// is at most 2^-25 / s <= 2^-39 of the JOINT maximum, far under the 2^-22-relative rounding the larger segment commits on its own
+// elements, and the joint maximum is also what bounds the output.  The same holds per output channel for the weights.
+// SEG2 = false is the one-segment kernel, instruction for instruction what it was (every use of the second segment is `if constexpr`).
+template <int WM, int WN, bool H = false, bool SEG2 = false>
 __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split_gemm_kernel(SplitArgs a) {
+    static_assert(H || !SEG2, "the second K segment exists in the fp16 form only");
     constexpr int XP = H ? 2 : 3;                    // activation planes (H: the fp16 form, see conv_split_kernel)
     constexpr int WPL = H ? 2 : 3;                   // weight planes
     constexpr int NT = 64 * WM * WN, NWAVE = WM * WN;
@@ -1471,6 +1491,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     const int img_first = __builtin_amdgcn_readfirstlane((int)pp_udiv(mfirst, a.dv_per)), img_last = __builtin_amdgcn_readfirstlane((int)pp_udiv(mlast, a.dv_per));
     unsigned oam_first = 0;                          // fp16 form: maximum of that sample (the epilogue's 1 / s)
     if constexpr (H) oam_first = a.x_amax[img_first];
+    if constexpr (SEG2) oam_first = max(oam_first, a.x2_amax[img_first]);       // (bit patterns of non-negative floats: integer order)
     const unsigned lds_base0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const size_t wstep0 = (size_t)a.ncb * (WPL * 64);
     f32x16 acc[2][4];                                // (zeroed right in front of the K loops: 128 live registers less during the set-up)
@@ -1503,6 +1524,17 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
         const int ho = (int)pp_udiv((unsigned)rem, a.dv_row), wo = rem - ho * a.W;
         gx[i] = (unsigned)(((img * a.xp_h + ho * a.stride) * a.xp_w + wo * a.stride) * a.Cin) * 4u + (unsigned)(((lane & 3) ^ ((pl >> 1) & 3)) * 16);
     }
+    unsigned gx2[SEG2 ? NXD : 1];                    // ... and of the second segment's stage seg1
+    if constexpr (SEG2) {
+#pragma unroll
+        for (int i = 0; i < NXD; ++i) {
+            const int pl = (wave + NWAVE * i) * 16 + (lane >> 2);
+            const unsigned m = (unsigned)min(m0 + pl, a.S - 1);
+            const int img = (int)pp_udiv(m, a.dv_per), rem = (int)(m - (unsigned)img * (unsigned)(a.H * a.W));
+            const int ho = (int)pp_udiv((unsigned)rem, a.dv_row), wo = rem - ho * a.W;
+            gx2[i] = (unsigned)(((img * a.xp2_h + ho * a.stride2) * a.xp2_w + wo * a.stride2) * a.Cin2) * 4u + (unsigned)(((lane & 3) ^ ((pl >> 1) & 3)) * 16);
+        }
+    }
     float xsc[4];                                    // activation scale of the sample of pixel pb * 32 + (lane & 31)
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb) xsc[pb] = pp_act_scale(oam_first);
@@ -1510,7 +1542,9 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb) {
             const unsigned mp = (unsigned)min(m0 + wm * 128 + pb * 32 + (lane & 31), a.S - 1);
-            xsc[pb] = pp_act_scale(a.x_amax[pp_udiv(mp, a.dv_per)]);
+            unsigned am = a.x_amax[pp_udiv(mp, a.dv_per)];
+            if constexpr (SEG2) am = max(am, a.x2_amax[pp_udiv(mp, a.dv_per)]);
+            xsc[pb] = pp_act_scale(am);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // (the maxima are in: from here on every vector-memory op is a DMA)
@@ -1525,10 +1559,17 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(wlane16 + (unsigned)(slab * 1024)), "s"(wsrc), "s"(dst) : "memory", "m0");
         }
         const float* xsrc = a.x + (size_t)c * 16;                                          // 64 bytes per stage
+        bool second = false;                                                               // (workgroup-uniform)
+        if constexpr (SEG2) {
+            second = c >= a.seg1;
+            if (second) xsrc = a.x2 + (size_t)(c - a.seg1) * 16;
+        }
 #pragma unroll
         for (int i = 0; i < NXD; ++i) {
             const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base0 + (unsigned)((c % XR) * XSTG + (wave + NWAVE * i) * 1024));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(gx[i]), "s"(xsrc), "s"(dst) : "memory", "m0");
+            unsigned g = gx[i];
+            if constexpr (SEG2) g = second ? gx2[i] : g;
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(g), "s"(xsrc), "s"(dst) : "memory", "m0");
         }
     };
     const int fofs = (wm * 128 + (lane & 31)) * 64 + ((((lane >> 5) * 2) ^ ((lane >> 1) & 3)) * 16);     // + pb * 2048; second quad: ^ 16
@@ -1764,7 +1805,9 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
 #pragma unroll
                 for (int pb = 0; pb < 4; ++pb) {
                     const unsigned mp = (unsigned)min(m0 + wm * 128 + pb * 32 + (lane & 31), a.S - 1);
-                    xinv[pb] = pp_act_unscale(a.x_amax[pp_udiv(mp, a.dv_per)]);
+                    unsigned am = a.x_amax[pp_udiv(mp, a.dv_per)];
+                    if constexpr (SEG2) am = max(am, a.x2_amax[pp_udiv(mp, a.dv_per)]);
+                    xinv[pb] = pp_act_unscale(am);
                 }
             }
         }
@@ -1867,6 +1910,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
         const int img = (int)pp_udiv((unsigned)m, a.dv_per), rem = (int)((unsigned)m - (unsigned)img * (unsigned)(a.H * a.W));
         float xi = 1.f, ymax = 0.f;
         if constexpr (H) xi = pp_act_unscale(a.x_amax[img]);
+        if constexpr (SEG2) xi = pp_act_unscale(max(a.x_amax[img], a.x2_amax[img]));
         rimg[pb] = img;
         const int oy = (int)pp_udiv((unsigned)rem, a.dv_row), ox = rem - oy * a.W;
         const size_t ypix = ((size_t)img * (a.H + a.y_pad) + oy) * (a.W + a.y_pad) + ox;
@@ -1957,6 +2001,17 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* w, uint
         o.w = h[pl][6] | ((unsigned)h[pl][7] << 16);
         out[(frag + pl) * 64 + lane] = o;
     }
+}
+
+// the packed weights ([K / 32][CoutPad][32], pack_conv order) of two 1x1 layers onto the same output channels as ONE layer over the
+// concatenated input channels (a folded shortcut: w over cin0 channels, then w2 over cin1); rows past cin0 + cin1 are zero
+__global__ __launch_bounds__(256) void concat_weights_kernel(const float* w, const float* w2, float* out, int cin0, int cin1, int CoutPad, size_t total) {
+    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;       // element of the output blob
+    if (i >= total) return;
+    const int e = (int)(i & 31), cout = (int)((i >> 5) % CoutPad);
+    const int k = (int)((i >> 5) / CoutPad) * 32 + (e & 7) * 4 + (e >> 3);          // inverse of 8 * (k & 3) + ((k & 31) >> 2)
+    auto at = [&](const float* src, int kk) { return src[((size_t)(kk >> 5) * CoutPad + cout) * 32 + 8 * (kk & 3) + ((kk & 31) >> 2)]; };
+    out[i] = k < cin0 ? at(w, k) : k < cin0 + cin1 ? at(w2, k - cin0) : 0.f;
 }
 
 // {m, sh} for pp_udiv (device): n / d for every 32-bit n; d == 1 is flagged by sh = 32
@@ -2358,7 +2413,14 @@ SplitPlan pp_conv_split_plan(const ConvArgs& a) {
         return p;
     // 3x3 stride 1 with 33 .. 48 output channels: conv_split48_kernel (three 16-channel blocks, K = two taps x 16 channels)
     const bool c48 = c48_on && k3 && ((a.Cout > 32 && a.Cout <= 48) || (c48_mult == 1 && a.Cout % 48 == 0) || (c48_mult == 2 && a.Cout == 192));
-    size_t steps = (size_t)(p.cin / 16) * p.taps;
+    // a folded shortcut (ConvArgs::Cin2): only as the second K segment of a plain 1x1 / stride-1 product in the fp16 form
+    if (a.Cin2 > 0) {
+        if (!(product && p.f16 && k1 && a.stride == 1 && !a.res1 && a.Cin2 % 16 == 0 && a.stride2 >= 1 && a.x_pad == 0 && a.x2_pad == 0 &&
+              (a.Hout - 1) * a.stride2 < a.Hin2 && (a.Wout - 1) * a.stride2 < a.Win2))
+            return SplitPlan();
+        p.cin2 = a.Cin2;
+    }
+    size_t steps = (size_t)((p.cin + p.cin2) / 16) * p.taps;
     if (product) {
         p.kernel = SPLIT_PRODUCT;
     } else if (!k3 && !s2p) {
@@ -2383,10 +2445,44 @@ SplitPlan pp_conv_split_plan(const ConvArgs& a) {
     }
     p.frag_bytes = (steps + 1) * p.ncb * wpl * 64 * sizeof(uint4);      // + one spare step: the kernel fetches one step ahead
     p.bytes = p.frag_bytes + (p.f16 ? (size_t)2 * p.nout * sizeof(float) : 0);   // fp16 form: 1 / c, then max |w| per output channel
+    if (p.cin2 > 0) {                                   // ... then the summed bias of the two segments
+        p.bias_off = (p.bytes + 15) / 16 * 16;
+        p.bytes = p.bias_off + (size_t)a.CoutPad * sizeof(float);
+    }
     return p;
 }
 
+// a folded shortcut (SplitPlan::cin2): the two layers' weights are concatenated along K into a temporary blob and split as ONE layer
+// -- one scale per output channel over both segments, fragments in stage order -- and the biases are added in float32 on the host
+static int split_weights_folded(const SplitPlan& p, const ConvArgs& a, void* out, hipStream_t stream) {
+    const int kcat = p.cin + p.cin2, kpad = (kcat + 31) / 32 * 32;
+    const size_t total = (size_t)kpad * a.CoutPad;
+    float* cat = nullptr;
+    PP_HIP_CHECK(hipMalloc((void**)&cat, total * sizeof(float)));
+    hipLaunchKernelGGL(concat_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.w, a.w2, cat, p.cin, p.cin2, a.CoutPad, total);
+    SplitPlan q = p;
+    q.cin = kcat;
+    q.cin2 = 0;
+    ConvArgs b = a;
+    b.w = cat;
+    b.Cin = kcat; b.K = kcat; b.Kpad = kpad;
+    int rc = pp_conv_split_weights(q, b, out, stream);
+    std::vector<float> b0(a.CoutPad), b1(a.CoutPad);
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = hipMemcpy(b0.data(), a.bias, b0.size() * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(b1.data(), a.bias2, b1.size() * sizeof(float), hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < b0.size(); ++i) b0[i] += b1[i];
+    if (e == hipSuccess) e = hipMemcpy(static_cast<unsigned char*>(out) + p.bias_off, b0.data(), b0.size() * sizeof(float), hipMemcpyHostToDevice);
+    (void)hipFree(cat);
+    if (rc == PP_OK && e != hipSuccess) {
+        pp_set_error("split_weights (folded shortcut) failed: %s", hipGetErrorString(e));
+        rc = PP_ERR_HIP;
+    }
+    return rc;
+}
+
 int pp_conv_split_weights(const SplitPlan& p, const ConvArgs& a, void* out, hipStream_t stream) {
+    if (p.cin2 > 0) return split_weights_folded(p, a, out, stream);
     float* cmax = nullptr;
     if (p.f16) {
         float* inv_scale = reinterpret_cast<float*>(static_cast<unsigned char*>(out) + p.frag_bytes);
@@ -2594,7 +2690,7 @@ int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stre
     static const int nw8_f16 = env_int("POSEPIPE_SPLIT_NW8_F16", 0);
     static const int nw8_min_blocks = env_int("POSEPIPE_SPLIT_NW8_MIN_BLOCKS", 512), nw8_min_chunks = env_int("POSEPIPE_SPLIT_NW8_MIN_CHUNKS", 16);
     static const int ring4_env = env_int("POSEPIPE_SPLIT_RING4", 1), ring48_env = env_int("POSEPIPE_SPLIT_RING48", 1);
-    const bool full = p.cin != a.Cin;
+    const bool full = p.cin != a.Cin;          // (a folded shortcut's channels are SplitPlan::cin2, not part of p.cin)
     SplitArgs s{};
     s.x = a.x; s.w = (const uint4*)a.wsplit; s.bias = a.bias; s.res1 = a.res1; s.res2 = a.res2; s.y = a.y;
     s.N = a.N; s.H = a.Hout; s.W = a.Wout; s.Cin = p.cin; s.Cout = a.Cout;
@@ -2606,7 +2702,16 @@ int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stre
     s.r1_shift = a.res1 ? a.res1_shift : 0;
     s.r1_H = a.res1 ? a.res1_H : a.Hout;
     s.r1_W = a.res1 ? a.res1_W : a.Wout;
-    s.nchunks = p.cin / 16;
+    s.nchunks = (p.cin + p.cin2) / 16;
+    s.seg1 = p.cin / 16;
+    if (p.cin2 > 0) {
+        if (p.cin2 != a.Cin2 || !a.x2 || !a.x2_amax || p.kernel != SPLIT_PRODUCT || !p.f16 || a.res1) {
+            pp_set_error("conv_split: the plan has a folded shortcut of %d channels, the launch does not match it", p.cin2);
+            return PP_ERR_STATE;
+        }
+        s.x2 = a.x2; s.x2_amax = a.x2_amax; s.Cin2 = a.Cin2; s.stride2 = a.stride2;
+        s.xp2_h = a.Hin2 + a.x2_pad; s.xp2_w = a.Win2 + a.x2_pad;
+    }
     s.ktaps = 1; s.KW = a.KW; s.pad = a.pad_h; s.Hin = a.Hin; s.Win = a.Win;
     if (p.kernel == SPLIT_TAP_GATHER) {     // a step per (chunk, tap), weights in the same [chunk][tap] order
         s.ktaps = p.taps;
@@ -2648,7 +2753,8 @@ int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stre
         // fp16 form: three raw float32 pixel stages of BM x 64 B + three weight stages; six-product form: two stages of split planes + weights
         const size_t lds_loop = f16 ? (size_t)3 * BM * 64 + (size_t)3 * BN * 2 * wpl * 16 : (size_t)2 * (xp * 2 * (BM + 4) * 16 + BN * 2 * wpl * 16);
         const size_t lds = std::max<size_t>(lds_loop, s.epi_lds ? (size_t)nwave * (16384 + 2048) : 0);
-        if (f16) launch_split<conv_split_gemm_kernel<2, 2, true>, 80 * 1024>(grid, 256, lds, stream, s);
+        if (p.cin2 > 0) launch_split<conv_split_gemm_kernel<2, 2, true, true>, 80 * 1024>(grid, 256, lds, stream, s);
+        else if (f16) launch_split<conv_split_gemm_kernel<2, 2, true>, 80 * 1024>(grid, 256, lds, stream, s);
         else launch_split<conv_split_gemm_kernel<2, 2, false>, 80 * 1024>(grid, 256, lds, stream, s);
         tag = "g256x128";
     } else if (p.kernel == SPLIT_S2P) {

@@ -133,6 +133,15 @@ struct ConvArgs {
     // per sample of what this launch stores (null: nobody needs it).  Device pointers to N slots each.
     const unsigned* x_amax;
     unsigned* y_amax;
+    // a folded projection shortcut (product kernel, fp16 form; SplitPlan::cin2): the op's product continues over a SECOND K segment --
+    // the 1x1 / pad-0 shortcut convolution of input x2 ([N][Hin2 + x2_pad][Win2 + x2_pad][Cin2], read at stride2) onto the same
+    // output pixels.  w2 / bias2: the shortcut's packed weights and bias (read at creation only: the split copy holds both segments'
+    // fragments and the summed bias, which `bias` then points at); x2_amax: the per-sample maxima of x2.  Cin2 == 0: none
+    const float* x2;
+    const float* w2;
+    const float* bias2;
+    const unsigned* x2_amax;
+    int Cin2, Hin2, Win2, stride2, x2_pad;
 };
 // ---- fp32 convolution on the bf16 matrix cores (three-way split; conv_split.hip) ----------------------------------------------
 // pixel tiling of a split tap kernel: output tiles of TH x TW (MODE_TILE), the padded input as one stream (MODE_STREAM) or 256 output
@@ -162,6 +171,8 @@ struct SplitPlan {
     int kernel = SPLIT_NONE;
     int f16 = 0;                // the split form of the weights and of the kernel
     int taps = 1, cin = 0;      // taps (9 / 1) and channels per tap (a full-cover 'valid' conv is a 1x1 over KH * KW * Cin)
+    int cin2 = 0;               // SPLIT_PRODUCT, fp16 form: channels of a folded shortcut's K segment (ConvArgs::Cin2), behind the op's own `cin`
+    size_t bias_off = 0;        // cin2 > 0: byte offset of the summed bias (CoutPad floats) in the split copy
     int ncb = 0;                // channel blocks of the split weights: 32 channels (SPLIT_C48: 16, whole columns of 3)
     int nout = 0;               // fp16 form: output channels of the scale block behind the fragments (1 / c, then max |w|)
     size_t frag_bytes = 0;      // the fragments (+ one spare step: the kernels fetch one step ahead) ...

@@ -122,9 +122,11 @@ def resnet50_body(pb, sd: dict, x, prefix: str):
         for b in range(blocks):
             q = f"backbone.layer{li + 1}.{b}."
             s = stride if b == 0 else 1
-            idn = cb(x, q + "downsample.0", q + "downsample.1", stride=s) if b == 0 else x
             y = cb(x, q + "conv1", q + "bn1", relu=R)
             y = cb(y, q + "conv2", q + "bn2", stride=s, pad=1, relu=R)
+            # the projection shortcut right in front of conv3: x stays alive (its buffer is not recycled) until then, which is what
+            # lets an fp16-form net fold the shortcut into conv3's product (pp_net_folded_into)
+            idn = cb(x, q + "downsample.0", q + "downsample.1", stride=s) if b == 0 else x
             x = cb(y, q + "conv3", q + "bn3", relu=R, res1=idn)
         feats.append(x)
     return feats

@@ -691,6 +691,12 @@ class Net:
         L.check(self.ctx.lib.pp_net_conv_kinds(self.handle, L.ptr(kinds)), "pp_net_conv_kinds")
         return kinds
 
+    def folded_into(self) -> np.ndarray:
+        """per op: the op that carries it (a projection shortcut folded into the product it was added to: never launched), else -1"""
+        into = np.zeros(len(self.prog.ops), dtype=np.int32)
+        L.check(self.ctx.lib.pp_net_folded_into(self.handle, L.ptr(into)), "pp_net_folded_into")
+        return into
+
     def profile(self, batch) -> np.ndarray:
         ms = np.zeros(len(self.prog.ops), dtype=np.float32)
         L.check(self.ctx.lib.pp_net_profile(self.handle, batch, L.ptr(ms)), "pp_net_profile")
