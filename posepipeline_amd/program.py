@@ -51,6 +51,21 @@ def pack_conv(weight, bias, cin_pad=None):
     return out, b
 
 
+# the fields of a pp_op that name a buffer the op READS; with "out", every field that holds a buffer id
+OPERAND_FIELDS = ("in_", "res1", "res2", "in2", "in3")
+# what a pp_op field holds where the op has no use for it (type, in_, out, cin and cout have no such value: every op states them)
+NEUTRAL_FIELDS = dict(res1=-1, res2=-1, kh=1, kw=1, stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
+                      res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=0, b_off=0, in2=-1, in3=-1, up2_log2=0,
+                      up3_log2=0)
+_OP_FIELDS = frozenset(f[0] for f in L.pp_op._fields_)
+
+
+def conv_out_dim(size, k, stride, pad, dil=1, pad_end=0):
+    """output rows (columns) of a convolution / pooling window over `size` input rows with `pad` zero rows on both sides and
+    `pad_end` more behind"""
+    return (size + pad_end + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
 @dataclass
 class VBuf:
     h: int
@@ -117,6 +132,24 @@ class ProgramBuilder:
         return off
 
     # ---- ops ---------------------------------------------------------------------------------
+    def _emit(self, type_, x, out, *, name, flops=0.0, **fields) -> int:
+        """append one op record: `fields` over NEUTRAL_FIELDS (every op gives cin and cout).  Returns `out`."""
+        unknown = set(fields) - _OP_FIELDS
+        assert not unknown, f"not a pp_op field: {sorted(unknown)}"
+        rec = dict(NEUTRAL_FIELDS, type=type_, in_=x, out=out, **fields)
+        assert set(rec) == _OP_FIELDS, sorted(_OP_FIELDS - set(rec))
+        self.vops.append(dict(rec, name=name, flops=flops))
+        return out
+
+    def _out_buf(self, out, h, w, c, out_c_off) -> int:
+        """where an op writes its [h][w][c] result: a new buffer (out is None), or channels [out_c_off, out_c_off + c) of `out`"""
+        if out is None:
+            assert out_c_off == 0
+            return self.buf(h, w, c)
+        oh, ow, oc = self.dims(out)
+        assert (oh, ow) == (h, w) and out_c_off + c <= oc and out_c_off % 4 == 0, (self.dims(out), h, w, c, out_c_off)
+        return out
+
     def conv(self, x, weight, bias, *, stride=1, pad=(0, 0), dil=(1, 1), relu=L.PP_RELU_NONE, res1=-1, res2=-1,
              up_log2=0, out=None, out_nchw=False, res1_shift=0, res1_off_w=0, out_c_off=0, pad_end=(0, 0),
              front_only=(0, 0), name="conv") -> int:
@@ -135,57 +168,29 @@ class ProgramBuilder:
         cout, cin, kh, kw = wt.shape
         assert cin <= cin_buf and cin_buf % 4 == 0, (cin, cin_buf)
         W, b = pack_conv(wt, bias, cin_pad=cin_buf)
-        ho = (h + pad_end[0] + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride + 1 - front_only[0]
-        wo = (w + pad_end[1] + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride + 1 - front_only[1]
-        if out is None:
-            assert out_c_off == 0
-            out = self.buf(ho << up_log2, wo << up_log2, cout)
-        else:
-            oh, ow, oc = self.dims(out)
-            assert (oh, ow) == (ho << up_log2, wo << up_log2) and out_c_off + cout <= oc and out_c_off % 4 == 0, \
-                (self.dims(out), ho, wo, cout, out_c_off)
-        w_off = self._add_blob(W)
-        b_off = self._add_blob(b)
-        self.vops.append(dict(type=L.PP_OP_CONV, in_=x, out=out, res1=res1, res2=res2, cin=cin_buf, cout=cout, kh=kh,
-                              kw=kw, stride=stride, pad_h=pad[0], pad_w=pad[1], dil_h=dil[0], dil_w=dil[1], relu=relu,
-                              up_log2=up_log2, out_nchw=int(out_nchw), res1_shift=res1_shift, res1_off_w=res1_off_w,
-                              out_c_off=out_c_off, in_c_off=0,
-                              pad_end=pad_end[0] | (pad_end[1] << 1) | (front_only[0] << 2) | (front_only[1] << 3),
-                              w_off=w_off, b_off=b_off, name=name,
-                              flops=2.0 * ho * wo * cout * cin * kh * kw))
-        return out
+        ho = conv_out_dim(h, kh, stride, pad[0], dil[0], pad_end[0]) - front_only[0]
+        wo = conv_out_dim(w, kw, stride, pad[1], dil[1], pad_end[1]) - front_only[1]
+        out = self._out_buf(out, ho << up_log2, wo << up_log2, cout, out_c_off)
+        return self._emit(L.PP_OP_CONV, x, out, res1=res1, res2=res2, cin=cin_buf, cout=cout, kh=kh, kw=kw, stride=stride,
+                          pad_h=pad[0], pad_w=pad[1], dil_h=dil[0], dil_w=dil[1], relu=relu, up_log2=up_log2, out_nchw=int(out_nchw),
+                          res1_shift=res1_shift, res1_off_w=res1_off_w, out_c_off=out_c_off,
+                          pad_end=pad_end[0] | (pad_end[1] << 1) | (front_only[0] << 2) | (front_only[1] << 3),
+                          w_off=self._add_blob(W), b_off=self._add_blob(b), name=name, flops=2.0 * ho * wo * cout * cin * kh * kw)
 
     def maxpool(self, x, k, stride, pad, name="maxpool", out=None, out_c_off=0, in_c_off=0, c=None) -> int:
         """c / in_c_off: pool channels [in_c_off, in_c_off + c) of x; out / out_c_off: into a slice of a wider buffer."""
         h, w, cx = self.dims(x)
         c = cx if c is None else c
         assert in_c_off + c <= cx and c % 4 == 0 and in_c_off % 4 == 0
-        ho = (h + 2 * pad - (k - 1) - 1) // stride + 1
-        wo = (w + 2 * pad - (k - 1) - 1) // stride + 1
-        if out is None:
-            assert out_c_off == 0
-            out = self.buf(ho, wo, c)
-        else:
-            oh, ow, oc = self.dims(out)
-            assert (oh, ow) == (ho, wo) and out_c_off + c <= oc and out_c_off % 4 == 0
-        self.vops.append(dict(type=L.PP_OP_MAXPOOL, in_=x, out=out, res1=-1, res2=-1, cin=c, cout=c, kh=k, kw=k,
-                              stride=stride, pad_h=pad, pad_w=pad, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
-                              res1_shift=0, res1_off_w=0, out_c_off=out_c_off, in_c_off=in_c_off, pad_end=0,
-                              w_off=0, b_off=0, name=name, flops=0.0))
-        return out
+        out = self._out_buf(out, conv_out_dim(h, k, stride, pad), conv_out_dim(w, k, stride, pad), c, out_c_off)
+        return self._emit(L.PP_OP_MAXPOOL, x, out, cin=c, cout=c, kh=k, kw=k, stride=stride, pad_h=pad, pad_w=pad, out_c_off=out_c_off,
+                          in_c_off=in_c_off, name=name)
 
     def avgpool(self, x, kh, kw, stride=1, name="avgpool") -> int:
         """nn.AvgPool2d((kh, kw), stride) without padding"""
         h, w, c = self.dims(x)
         out = self.buf((h - kh) // stride + 1, (w - kw) // stride + 1, c)
-        return self._plain_op(L.PP_OP_AVGPOOL, x, out, cin=c, cout=c, kh=kh, kw=kw, stride=stride, name=name)
-
-    def _plain_op(self, type_, x, out, *, cin, cout, kh=1, kw=1, stride=1, w_off=0, name="op", flops=0.0):
-        self.vops.append(dict(type=type_, in_=x, out=out, res1=-1, res2=-1, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride,
-                              pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0,
-                              res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=0, name=name,
-                              flops=flops))
-        return out
+        return self._emit(L.PP_OP_AVGPOOL, x, out, cin=c, cout=c, kh=kh, kw=kw, stride=stride, name=name)
 
     def vit_encoder(self, x, params, *, depth, heads, mlp_ratio, name="vit_encoder") -> int:
         """PP_OP_VIT_ENCODER on a [h][w][dim] fp32 token map.  params: flat fp32 block in the layout of
@@ -197,8 +202,8 @@ class ProgramBuilder:
         assert params.size == t * dim + per_block * depth + 2 * dim, (params.size, t, dim, depth)
         out = self.buf(h, w, dim)
         macs = depth * (t * (4 * dim * dim + 2 * dim * hid) + 2 * t * t * dim)
-        return self._plain_op(L.PP_OP_VIT_ENCODER, x, out, cin=dim, cout=dim, kh=depth, kw=heads, stride=mlp_ratio,
-                              w_off=self._add_blob(params), name=name, flops=2.0 * macs)
+        return self._emit(L.PP_OP_VIT_ENCODER, x, out, cin=dim, cout=dim, kh=depth, kw=heads, stride=mlp_ratio,
+                          w_off=self._add_blob(params), name=name, flops=2.0 * macs)
 
     def upsample_add(self, t, *, up_log2, res1=-1, res2=-1, relu=L.PP_RELU_NONE, name="upsample_add", more=()) -> int:
         """out = act((((res1 + up(t, 2^up_log2)) + up(t2, 2^u2)) + up(t3, 2^u3)) + res2): the accumulate step(s) of an HRNet fuse
@@ -210,11 +215,8 @@ class ProgramBuilder:
         for tb, ub in more:
             assert self.dims(tb) == ((h << up_log2) >> ub, (w << up_log2) >> ub, c), (self.dims(tb), self.dims(out), ub)
         (in2, up2), (in3, up3) = (more + [(-1, 0), (-1, 0)])[:2]
-        self.vops.append(dict(type=L.PP_OP_UPSAMPLE_ADD, in_=t, out=out, res1=res1, res2=res2, cin=c, cout=c, kh=1, kw=1,
-                              stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=relu, up_log2=up_log2, out_nchw=0,
-                              res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name,
-                              in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, flops=0.0))
-        return out
+        return self._emit(L.PP_OP_UPSAMPLE_ADD, t, out, res1=res1, res2=res2, cin=c, cout=c, relu=relu, up_log2=up_log2, in2=in2, in3=in3,
+                          up2_log2=up2, up3_log2=up3, name=name)
 
     def bilinear_add(self, t, *, up_log2, res1=-1, relu=L.PP_RELU_NONE, more=(), out=None, out_c_off=0,
                      name="bilinear_add") -> int:
@@ -225,12 +227,8 @@ class ProgramBuilder:
         h, w, c = self.dims(t)
         assert c % 4 == 0 and 0 <= up_log2 <= 5, (c, up_log2)
         ho, wo = h << up_log2, w << up_log2
-        if out is None:
-            assert out_c_off == 0
-            out = self.buf(ho, wo, c)
-        else:
-            oh, ow, oc = self.dims(out)
-            assert (oh, ow) == (ho, wo) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + c <= oc, (self.dims(out), ho, wo, c, out_c_off)
+        out = self._out_buf(out, ho, wo, c, out_c_off)
+        assert self.dims(out)[2] % 4 == 0, self.dims(out)
         if res1 >= 0:
             assert self.dims(res1) == (ho, wo, c), (self.dims(res1), ho, wo, c)
         more = list(more)
@@ -239,11 +237,8 @@ class ProgramBuilder:
             assert 0 <= ub <= 5 and self.dims(tb) == (ho >> ub, wo >> ub, c) and (ho >> ub << ub, wo >> ub << ub) == (ho, wo), \
                 (self.dims(tb), ho, wo, ub)
         (in2, up2), (in3, up3) = (more + [(-1, 0), (-1, 0)])[:2]
-        self.vops.append(dict(type=L.PP_OP_BILINEAR_ADD, in_=t, out=out, res1=res1, res2=-1, cin=c, cout=c, kh=1, kw=1,
-                              stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=relu, up_log2=up_log2, out_nchw=0,
-                              res1_shift=0, res1_off_w=0, out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name,
-                              in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, flops=0.0))
-        return out
+        return self._emit(L.PP_OP_BILINEAR_ADD, t, out, res1=res1, cin=c, cout=c, relu=relu, up_log2=up_log2, out_c_off=out_c_off,
+                          in2=in2, in3=in3, up2_log2=up2, up3_log2=up3, name=name)
 
     # ---- HRFormer block ops (PP_OP_DWCONV3X3 / _LAYERNORM / _WINDOW_ATTN / _GELU_ADD; include/posepipe_hip.h) -------------------
     def dwconv3x3(self, x, weight, bias, *, stride=1, act=L.PP_RELU_NONE, gelu_in=False, name="dwconv3x3") -> int:
@@ -261,14 +256,9 @@ class ProgramBuilder:
         if bias is not None:
             bk[:c] = np.asarray(bias, np.float32)
         ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-        out = self.buf(ho, wo, c_buf)
-        w_off = self._add_blob(wk)
-        b_off = self._add_blob(bk)
-        self.vops.append(dict(type=L.PP_OP_DWCONV3X3, in_=x, out=out, res1=-1, res2=-1, cin=c_buf, cout=c_buf, kh=3, kw=3,
-                              stride=stride, pad_h=1, pad_w=1, dil_h=1, dil_w=1, relu=act, up_log2=0, out_nchw=0, res1_shift=0,
-                              res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=L.PP_DW_GELU_IN if gelu_in else 0, w_off=w_off,
-                              b_off=b_off, name=name, flops=2.0 * ho * wo * c * 9))
-        return out
+        return self._emit(L.PP_OP_DWCONV3X3, x, self.buf(ho, wo, c_buf), cin=c_buf, cout=c_buf, kh=3, kw=3, stride=stride, pad_h=1,
+                          pad_w=1, relu=act, pad_end=L.PP_DW_GELU_IN if gelu_in else 0, w_off=self._add_blob(wk),
+                          b_off=self._add_blob(bk), name=name, flops=2.0 * ho * wo * c * 9)
 
     def layernorm(self, x, gamma, beta, *, eps=1e-6, name="layernorm") -> int:
         """LayerNorm over the channels of every pixel.  gamma / beta: [c_real], c_real <= the buffer's channels; the padding
@@ -282,13 +272,8 @@ class ProgramBuilder:
         bk = np.zeros(c_buf + 1, np.float32)
         bk[:c] = np.asarray(beta, np.float32).reshape(-1)
         bk[c_buf] = eps
-        out = self.buf(h, w, c_buf)
-        w_off = self._add_blob(gk)
-        b_off = self._add_blob(bk)
-        self.vops.append(dict(type=L.PP_OP_LAYERNORM, in_=x, out=out, res1=-1, res2=-1, cin=c, cout=c_buf, kh=1, kw=1, stride=1,
-                              pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
-                              out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, flops=8.0 * h * w * c))
-        return out
+        return self._emit(L.PP_OP_LAYERNORM, x, self.buf(h, w, c_buf), cin=c, cout=c_buf, w_off=self._add_blob(gk),
+                          b_off=self._add_blob(bk), name=name, flops=8.0 * h * w * c)
 
     def window_attention(self, qkv, table, qkv_bias, *, c_real, heads, window=7, name="window_attn") -> int:
         """7x7 window attention on a qkv map [h][w][3 * c_buf] (channel s * c_buf + head * hd + d; a 1x1 convolution of the
@@ -301,16 +286,10 @@ class ProgramBuilder:
         assert tb.shape == ((2 * window - 1) ** 2, heads), tb.shape
         bq = np.zeros((3, c_buf), np.float32)
         bq[:, :c_real] = np.asarray(qkv_bias, np.float32).reshape(3, c_real)
-        out = self.buf(h, w, c_buf)
-        w_off = self._add_blob(tb)
-        b_off = self._add_blob(bq)
         t = window * window
         n_win = -(-h // window) * -(-w // window)
-        self.vops.append(dict(type=L.PP_OP_WINDOW_ATTN, in_=qkv, out=out, res1=-1, res2=-1, cin=c_real, cout=c_buf, kh=window,
-                              kw=window, stride=heads, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
-                              res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name,
-                              flops=2.0 * n_win * 2 * t * t * c_real))
-        return out
+        return self._emit(L.PP_OP_WINDOW_ATTN, qkv, self.buf(h, w, c_buf), cin=c_real, cout=c_buf, kh=window, kw=window, stride=heads,
+                          w_off=self._add_blob(tb), b_off=self._add_blob(bq), name=name, flops=2.0 * n_win * 2 * t * t * c_real)
 
     def attention(self, qkv, *, c_real, heads, name="attention") -> int:
         """Global float32 multi-head self-attention (PP_OP_ATTENTION) on a qkv map [h][w][3 * c_buf] (channel s * c_buf + head * hd + d;
@@ -323,17 +302,13 @@ class ProgramBuilder:
         assert hd % 4 == 0 and hd <= 128 and h * w <= 128, (hd, h, w)
         out = self.buf(h, w, c_buf)
         t = h * w
-        return self._plain_op(L.PP_OP_ATTENTION, qkv, out, cin=c_real, cout=c_buf, stride=heads, name=name, flops=2.0 * 2 * t * t * c_real)
+        return self._emit(L.PP_OP_ATTENTION, qkv, out, cin=c_real, cout=c_buf, stride=heads, name=name, flops=2.0 * 2 * t * t * c_real)
 
     def gelu_add(self, x, *, res1=-1, name="gelu_add") -> int:
         """out = res1 + gelu(x)  (res1 = -1: gelu(x))"""
         h, w, c = self.dims(x)
         assert c % 4 == 0 and (res1 < 0 or self.dims(res1) == (h, w, c))
-        out = self.buf(h, w, c)
-        self.vops.append(dict(type=L.PP_OP_GELU_ADD, in_=x, out=out, res1=res1, res2=-1, cin=c, cout=c, kh=1, kw=1, stride=1, pad_h=0,
-                              pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0, out_c_off=0,
-                              in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, flops=0.0))
-        return out
+        return self._emit(L.PP_OP_GELU_ADD, x, self.buf(h, w, c), res1=res1, cin=c, cout=c, name=name)
 
     # ---- DLA-34's DCN up-sampling head (PP_OP_DCN3X3 / PP_OP_DWDECONV; include/posepipe_hip.h) ----------------------------------
     def dcn3x3(self, x, offset_mask, weight, bias, *, relu=L.PP_RELU_NONE, name="dcn3x3") -> int:
@@ -352,14 +327,9 @@ class ProgramBuilder:
         bk = np.zeros(cout_p, np.float32)
         if bias is not None:
             bk[:cout] = np.asarray(bias, np.float32)
-        out = self.buf(h, w, cout)
-        w_off = self._add_blob(wk)
-        b_off = self._add_blob(bk)
-        self.vops.append(dict(type=L.PP_OP_DCN3X3, in_=x, out=out, res1=-1, res2=-1, cin=cin_buf, cout=cout, kh=3, kw=3, stride=1,
-                              pad_h=1, pad_w=1, dil_h=1, dil_w=1, relu=relu, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
-                              out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, in2=offset_mask, in3=-1,
-                              up2_log2=0, up3_log2=0, flops=2.0 * 9 * cin * cout * h * w))
-        return out
+        return self._emit(L.PP_OP_DCN3X3, x, self.buf(h, w, cout), cin=cin_buf, cout=cout, kh=3, kw=3, pad_h=1, pad_w=1, relu=relu,
+                          in2=offset_mask, w_off=self._add_blob(wk), b_off=self._add_blob(bk), name=name,
+                          flops=2.0 * 9 * cin * cout * h * w)
 
     def dwdeconv(self, x, weight, stride, *, res1=-1, name="dwdeconv") -> int:
         """Depthwise ConvTranspose2d(c, c, 2 * stride, stride, padding stride // 2, groups=c, bias=False).  weight: torch layout
@@ -373,38 +343,27 @@ class ProgramBuilder:
         out = self.buf(h * stride, w * stride, c_buf)
         if res1 >= 0:
             assert self.dims(res1) == self.dims(out), (self.dims(res1), self.dims(out))
-        w_off = self._add_blob(wk)
-        self.vops.append(dict(type=L.PP_OP_DWDECONV, in_=x, out=out, res1=res1, res2=-1, cin=c_buf, cout=c_buf, kh=k, kw=k,
-                              stride=stride, pad_h=stride // 2, pad_w=stride // 2, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0,
-                              res1_shift=0, res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=0, name=name,
-                              flops=2.0 * 4 * c * h * w * stride * stride))
-        return out
+        return self._emit(L.PP_OP_DWDECONV, x, out, res1=res1, cin=c_buf, cout=c_buf, kh=k, kw=k, stride=stride, pad_h=stride // 2,
+                          pad_w=stride // 2, w_off=self._add_blob(wk), name=name, flops=2.0 * 4 * c * h * w * stride * stride)
 
     # ---- TraDeS' program B (PP_OP_SUB_CAT / PP_OP_BCAST_MUL / PP_OP_BLEND2; include/posepipe_hip.h) -------------------------------
-    def _ew_op(self, type_, x, out, *, res1=-1, in2=-1, in3=-1, name="op") -> int:
-        self.vops.append(dict(type=type_, in_=x, out=out, res1=res1, res2=-1, cin=self.dims(x)[2], cout=self.dims(out)[2], kh=1, kw=1,
-                              stride=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
-                              out_c_off=0, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, in2=in2, in3=in3, up2_log2=0, up3_log2=0,
-                              flops=0.0))
-        return out
-
     def sub_cat(self, a, b, lead, name="sub_cat") -> int:
         """[h][w][4 + c]: channels [0, c2) = lead ([h][w][c2 <= 4]), [c2, 4) zeros, [4, 4 + c) = a - b"""
         h, w, c = self.dims(a)
         assert self.dims(b) == (h, w, c) and c % 4 == 0 and self.dims(lead)[:2] == (h, w) and 1 <= self.dims(lead)[2] <= 4
-        return self._ew_op(L.PP_OP_SUB_CAT, a, self.buf(h, w, c + 4), res1=b, in2=lead, name=name)
+        return self._emit(L.PP_OP_SUB_CAT, a, self.buf(h, w, c + 4), res1=b, in2=lead, cin=c, cout=c + 4, name=name)
 
     def bcast_mul(self, x, gate, name="bcast_mul") -> int:
         """gate [h][w][1] * x [h][w][c]"""
         h, w, c = self.dims(x)
         assert c % 4 == 0 and self.dims(gate) == (h, w, 1)
-        return self._ew_op(L.PP_OP_BCAST_MUL, x, self.buf(h, w, c), in2=gate, name=name)
+        return self._emit(L.PP_OP_BCAST_MUL, x, self.buf(h, w, c), in2=gate, cin=c, cout=c, name=name)
 
     def blend2(self, x0, x1, logit0, logit1, name="blend2") -> int:
         """a0 x0 + a1 x1 with (a0, a1) = softmax(logit0, logit1) per pixel; logits [h][w][1]"""
         h, w, c = self.dims(x0)
         assert c % 4 == 0 and self.dims(x1) == (h, w, c) and self.dims(logit0) == (h, w, 1) and self.dims(logit1) == (h, w, 1)
-        return self._ew_op(L.PP_OP_BLEND2, x0, self.buf(h, w, c), res1=x1, in2=logit0, in3=logit1, name=name)
+        return self._emit(L.PP_OP_BLEND2, x0, self.buf(h, w, c), res1=x1, in2=logit0, in3=logit1, cin=c, cout=c, name=name)
 
     # ---- GAST-Net's graph-attention blocks (PP_OP_GRAPH_MIX / PP_OP_JOINT_ATTN; include/posepipe_hip.h) ------------------------------
     def graph_mix(self, x, mats, biases, masks, *, relu=L.PP_RELU_NONE, out=None, out_c_off=0, name="graph_mix") -> int:
@@ -421,20 +380,14 @@ class ProgramBuilder:
             m = np.asarray(m, bool)
             assert a.shape == (17, 17, c) and m.shape == (17, 17) and not a[~m].any(), (a.shape, m.shape)
             bits.append([sum(1 << i for i in range(17) if m[j, i]) for j in range(17)])
-        if out is None:
-            assert out_c_off == 0
-            out = self.buf(h, w, g * c)
-        else:
-            oh, ow, oc = self.dims(out)
-            assert (oh, ow) == (h, w) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + g * c <= oc, (self.dims(out), h, w, g * c, out_c_off)
+        out = self._out_buf(out, h, w, g * c, out_c_off)
+        assert self.dims(out)[2] % 4 == 0, self.dims(out)
         w_off = self._add_blob(np.stack(mats))
         b_off = self._add_blob(np.concatenate([np.stack([np.asarray(b, np.float32).reshape(c) for b in biases]).reshape(-1),
                                                np.asarray(bits, np.float32).reshape(-1)]))
         nnz = sum(int(np.asarray(m, bool).sum()) for m in masks)
-        self.vops.append(dict(type=L.PP_OP_GRAPH_MIX, in_=x, out=out, res1=-1, res2=-1, cin=cin, cout=g * c, kh=g, kw=1, stride=1, pad_h=0,
-                              pad_w=0, dil_h=1, dil_w=1, relu=relu, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
-                              out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name, flops=2.0 * w * c * nnz))
-        return out
+        return self._emit(L.PP_OP_GRAPH_MIX, x, out, cin=cin, cout=g * c, kh=g, relu=relu, out_c_off=out_c_off, w_off=w_off, b_off=b_off,
+                          name=name, flops=2.0 * w * c * nnz)
 
     def joint_attention(self, qkv, *, c_real, heads, out=None, out_c_off=0, name="joint_attn") -> int:
         """Per time step, multi-head attention over the 17 joints, no scale (PP_OP_JOINT_ATTN), on a qkv map [17][w][3 * c_buf] in
@@ -444,16 +397,10 @@ class ProgramBuilder:
         assert h == 17 and c3 == 3 * c_buf and c_buf % 4 == 0 and c_real <= c_buf and c_real % heads == 0, (h, c3, c_real, heads)
         hd = c_real // heads
         assert hd % 4 == 0 and hd <= 128, hd
-        if out is None:
-            assert out_c_off == 0
-            out = self.buf(h, w, c_buf)
-        else:
-            oh, ow, oc = self.dims(out)
-            assert (oh, ow) == (h, w) and out_c_off % 4 == 0 and oc % 4 == 0 and out_c_off + c_buf <= oc, (self.dims(out), h, w, c_buf, out_c_off)
-        self.vops.append(dict(type=L.PP_OP_JOINT_ATTN, in_=qkv, out=out, res1=-1, res2=-1, cin=c_real, cout=c_buf, kh=1, kw=1, stride=heads,
-                              pad_h=0, pad_w=0, dil_h=1, dil_w=1, relu=0, up_log2=0, out_nchw=0, res1_shift=0, res1_off_w=0,
-                              out_c_off=out_c_off, in_c_off=0, pad_end=0, w_off=0, b_off=0, name=name, flops=2.0 * 2 * w * 17 * 17 * c_real))
-        return out
+        out = self._out_buf(out, h, w, c_buf, out_c_off)
+        assert self.dims(out)[2] % 4 == 0, self.dims(out)
+        return self._emit(L.PP_OP_JOINT_ATTN, qkv, out, cin=c_real, cout=c_buf, stride=heads, out_c_off=out_c_off, name=name,
+                          flops=2.0 * 2 * w * 17 * 17 * c_real)
 
     def deconv4x4s2_bf16(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv_bf16") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as ONE bf16 GEMM over the 16 kernel taps +
@@ -469,21 +416,16 @@ class ProgramBuilder:
                     for s in (0, 1):
                         blocks[a, b, r, s] = wt[:, :, 3 - a - 2 * r, 3 - b - 2 * s].T
         bb = np.zeros(cout, np.float32) if bias is None else np.asarray(bias, np.float32)
-        out = self.buf(2 * h, 2 * w, cout)
-        w_off = self._add_blob(blocks)
-        b_off = self._add_blob(bb)
-        self.vops.append(dict(type=L.PP_OP_DECONV_BF16, in_=x, out=out, res1=-1, res2=-1, cin=cin, cout=cout, kh=4, kw=4,
-                              stride=2, pad_h=1, pad_w=1, dil_h=1, dil_w=1, relu=relu, up_log2=0, out_nchw=0, res1_shift=0,
-                              res1_off_w=0, out_c_off=0, in_c_off=0, pad_end=0, w_off=w_off, b_off=b_off, name=name,
-                              flops=2.0 * h * w * cin * cout * 16))
-        return out
+        return self._emit(L.PP_OP_DECONV_BF16, x, self.buf(2 * h, 2 * w, cout), cin=cin, cout=cout, kh=4, kw=4, stride=2, pad_h=1, pad_w=1,
+                          relu=relu, w_off=self._add_blob(blocks), b_off=self._add_blob(bb), name=name,
+                          flops=2.0 * h * w * cin * cout * 16)
 
     def depth_to_space(self, x, name="depth_to_space") -> int:
         """[h][w][4c] (channel groups g = 2*dy + dx) -> [2h][2w][c]"""
         h, w, c4 = self.dims(x)
         assert c4 % 16 == 0
         out = self.buf(2 * h, 2 * w, c4 // 4)
-        return self._plain_op(L.PP_OP_DEPTH_TO_SPACE, x, out, cin=c4, cout=c4 // 4, name=name)
+        return self._emit(L.PP_OP_DEPTH_TO_SPACE, x, out, cin=c4, cout=c4 // 4, name=name)
 
     def deconv4x4s2(self, x, weight, bias, *, relu=L.PP_RELU_NONE, name="deconv") -> int:
         """ConvTranspose2d(kernel 4, stride 2, padding 1) (+ folded BN, ReLU) as four 2x2 convolutions, one per output
@@ -520,19 +462,18 @@ class ProgramBuilder:
         need = [0] * n_v
         for op in self.vops:
             conv = op["type"] == L.PP_OP_CONV
-            for k in ("in_", "out", "res1", "res2", "in2", "in3"):
-                v = op.get(k, -1)
-                if v >= 0 and not conv:
-                    ok[v] = False
             if not conv:
+                for k in OPERAND_FIELDS + ("out",):
+                    if op[k] >= 0:
+                        ok[op[k]] = False
                 continue
             o = op["out"]
             if op["out_nchw"] or op["out_c_off"] or self.vbufs[o].c != op["cout"]:
                 ok[o] = False                       # channel slices / NCHW planes: dense
             h, w, _ = self.dims(op["in_"])
             eh, ew = op["pad_end"] & 1, (op["pad_end"] >> 1) & 1
-            ho = (h + eh + 2 * op["pad_h"] - op["dil_h"] * (op["kh"] - 1) - 1) // op["stride"] + 1 - ((op["pad_end"] >> 2) & 1)
-            wo = (w + ew + 2 * op["pad_w"] - op["dil_w"] * (op["kw"] - 1) - 1) // op["stride"] + 1 - ((op["pad_end"] >> 3) & 1)
+            ho = conv_out_dim(h, op["kh"], op["stride"], op["pad_h"], op["dil_h"], eh) - ((op["pad_end"] >> 2) & 1)
+            wo = conv_out_dim(w, op["kw"], op["stride"], op["pad_w"], op["dil_w"], ew) - ((op["pad_end"] >> 3) & 1)
             over = max(op["pad_h"], op["pad_w"], (ho - 1) * op["stride"] - op["pad_h"] + (op["kh"] - 1) * op["dil_h"] - (h - 1),
                        (wo - 1) * op["stride"] - op["pad_w"] + (op["kw"] - 1) * op["dil_w"] - (w - 1))
             if over > 0:
@@ -544,10 +485,9 @@ class ProgramBuilder:
         last_use = [-1] * n_v
         first_def = [None] * n_v
         for i, op in enumerate(self.vops):
-            for key in ("in_", "res1", "res2", "in2", "in3", "out"):
-                v = op.get(key, -1)
-                if v >= 0:
-                    last_use[v] = i
+            for key in OPERAND_FIELDS + ("out",):
+                if op[key] >= 0:
+                    last_use[op[key]] = i
             if first_def[op["out"]] is None:
                 first_def[op["out"]] = i
         vpad = self._halo_plan()
@@ -567,7 +507,7 @@ class ProgramBuilder:
                 key = self.dims(v) + (vpad[v],)
                 pool = free.get(key, [])
                 # never alias an operand of this very op
-                busy = {v2p[op[k]] for k in ("in_", "res1", "res2", "in2", "in3") if op.get(k, -1) >= 0}
+                busy = {v2p[op[k]] for k in OPERAND_FIELDS if op[k] >= 0}
                 pick = next((p for p in pool if p not in busy), None)
                 if pick is not None:
                     pool.remove(pick)
@@ -577,8 +517,8 @@ class ProgramBuilder:
                     phys_pad.append(vpad[v])
                     v2p[v] = len(phys_dims) - 1
             # release operands whose last use is this op
-            for key in ("in_", "res1", "res2", "in2", "in3", "out"):
-                u = op.get(key, -1)
+            for key in OPERAND_FIELDS + ("out",):
+                u = op[key]
                 if u >= 0 and last_use[u] == i and not self.vbufs[u].pinned and v2p[u] >= 0:
                     lst = free.setdefault(self.dims(u) + (vpad[u],), [])
                     if v2p[u] not in lst:
@@ -589,7 +529,7 @@ class ProgramBuilder:
             for k, val in op.items():
                 if k in ("name", "flops"):
                     continue
-                if k in ("in_", "out", "res1", "res2", "in2", "in3"):
+                if k == "out" or k in OPERAND_FIELDS:
                     val = v2p[val] if val >= 0 else -1
                 setattr(rec, k, int(val))
             ops.append(rec)
