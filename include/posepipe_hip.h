@@ -280,9 +280,15 @@ int pp_net_buffer(pp_net* net, int buf, void** dptr, size_t* bytes_per_sample);
  * (max_batch uint32: the bit pattern of max |x| over sample n, any upper bound >= it is valid), or NULL when no fp16-form
  * convolution reads `buf` (nothing to do).  The call is a ONE-SHOT promise: it covers the NEXT pp_net_run / pp_net_profile /
  * pp_net_capture whose op range reads `buf` -- the caller fills the array on the ctx stream before that run and calls this again
- * before every further one; a run without a fresh promise takes the maxima itself, and pp_net_forward (which overwrites the
- * buffer) voids a pending promise.  The address is stable for the life of the net.  (The detector's preprocess kernel and
- * RoIAlign do this.) */
+ * before every further one; an eager (not replayed) run without a fresh promise takes the maxima itself, and pp_net_forward
+ * (which overwrites the buffer) voids a pending promise.
+ * A captured graph fixes "promised / not promised" at CAPTURE time, not at replay:
+ *  - captured with no promise pending, the graph holds the maxima pass, and every replay takes the maxima itself.  A promise made
+ *    before such a replay changes nothing in it and is consumed by it: it never carries over to a later run;
+ *  - captured under a promise, the graph holds NO maxima pass, and EVERY replay reads the caller's array as it stands then: the
+ *    caller refills it on the ctx stream before each replay.  No further call of this function is needed for a replay (one made is
+ *    consumed by it), and a run that is not a replay (another batch, an op range) still takes the maxima itself.
+ * The address is stable for the life of the net.  (The detector's preprocess kernel and RoIAlign do this.) */
 int pp_net_input_amax(pp_net* net, int buf, void** dptr);
 /* run ops [first, last) for `batch` samples (last < 0: to the end); inputs must already be in their buffers */
 int pp_net_run(pp_net* net, int batch, int first_op, int last_op);
@@ -298,7 +304,10 @@ int pp_net_set_lanes(pp_net* net, int enable);
  * tails (HRNet at 256x192), large maps that fill the chip on their own only disturb each other (measured round 6: the 1080p cascade
  * runs 3 % faster on 2 lanes than on 4).  Results are identical for any count. */
 int pp_net_set_lane_count(pp_net* net, int n_lanes);
-/* capture ops [0, n_ops) at `batch` into a hipGraph and replay it on later pp_net_run calls */
+/* capture ops [0, n_ops) at `batch` into a hipGraph and replay it on later pp_net_run calls of the whole program at that batch (any
+ * other batch or op range runs eagerly).  The capture counts as the run a pending pp_net_input_amax promise covers, and it fixes
+ * that choice for every replay: captured under a promise, the graph has no maxima pass for that input and each replay reads the
+ * caller's array; captured without one, each replay takes the maxima itself whatever is promised later. */
 int pp_net_capture(pp_net* net, int batch);
 /* per-op elapsed time of the last profiled run (HIP events around each op), ms; NULL-safe */
 int pp_net_profile(pp_net* net, int batch, float* ms_per_op);
@@ -596,7 +605,8 @@ int pp_detector_collect(pp_detector* d, float* dets, int32_t* n_dets, float* pro
 #define PP_DET_MARGIN_DET_TOP 6
 #define PP_DET_MARGIN_DET_ORDER 7
 int pp_detector_enable_margins(pp_detector* d, int enable, float score_weight);
-/* margins [n_frames][PP_DET_N_MARGINS] of the most recent pp_detector_run (n_frames = that run's) */
+/* margins [n_frames][PP_DET_N_MARGINS] of the most recent pp_detector_run / collected pass (n_frames = that pass's).  Refused
+ * while a pass is in flight (between pp_detector_enqueue and pp_detector_collect): its margins are published by the collect. */
 int pp_detector_margins(pp_detector* d, int n_frames, float* margins);
 
 /* Regression of caller-supplied boxes through the RoI head (Tracktor's track propagation: mmtrack TracktorTracker.regress_tracks ->

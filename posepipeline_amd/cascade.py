@@ -62,7 +62,8 @@ class Cascade:
                  batched_lift: bool = True):
         """blob_fn(name, program) -> (device pointer, n_floats) or None, name in "det_a", "det_b", "pose", "lift" (called in
         that order): a weight blob that is already resident on the device -- parallel.broadcast_blob_device delivers rank
-        0's over RCCL; the *_sd arguments then only define the program structure (ops, buffers, blob offsets).
+        0's over RCCL; the *_sd arguments then only define the program structure (ops, buffers, blob offsets).  Not with
+        id_numerics="certified" (ValueError): the exact detector of its re-runs takes its weights from det_sd.
         overlap_detector: the look-ahead of the detector pass -- None / True / "stream" (default): the detector gets its own context
         (HIP stream + lanes) and `step(..., prefetch=next chunk)` ENQUEUES its pass over the next chunk there (pp_detector_enqueue:
         asynchronous, no thread); the next step collects it.  "pipeline": the same on the cascade's one stream; False / "off": none.
@@ -86,6 +87,11 @@ class Cascade:
         self.certified = id_numerics == "certified"
         if self.certified:
             assert tracking == "MMTrack_deepsort" and reid_sd is None, "certified ids: the Faster-RCNN + SORT configuration"
+            # the exact detector of the re-runs is built from det_sd itself (blob_fn's broadcast protocol hands out every program's
+            # blob once, in a fixed order): where det_sd only defines the structure, it would re-run frames on placeholder weights
+            if blob_fn is not None:
+                raise ValueError("Cascade: id_numerics='certified' cannot be combined with blob_fn (the exact detector of the "
+                                 "re-runs takes its weights from det_sd, which blob_fn makes a placeholder on every rank but the source)")
             id_numerics = "split"
         id_numerics = numerics if id_numerics is None else id_numerics
         self.ctx = ctx
@@ -197,6 +203,9 @@ class Cascade:
             net = getattr(self, name, None)
             if net is not None:
                 net.close()
+        # the "stream" look-ahead's own context (everything that lived on it is closed above); the caller's ctx stays the caller's
+        if self.det_ctx is not self.ctx:
+            self.det_ctx.close()
 
     def __del__(self):
         try:

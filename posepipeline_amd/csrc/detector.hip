@@ -46,8 +46,9 @@ struct pp_detector {
     float score_weight = 0.f;
     float *d_margins = nullptr, *cut_gap = nullptr;
     unsigned char *kflag1 = nullptr, *kflag2 = nullptr;
-    std::vector<float> h_margins;
-    int h_margins_frames = 0;
+    float* h_margins = nullptr;  // page-locked, like h_dets: the copy into it is truly asynchronous
+    int h_margins_frames = 0;    // frames of margins the last COLLECTED pass left in h_margins (published by pp_detector_collect)
+    int pending_margins = 0;     // frames of margins the pass in flight is copying into h_margins
     // asynchronous form (pp_detector_enqueue / pp_detector_collect): page-locked staging of the pass's outputs and its completion event
     float *h_dets = nullptr, *h_props = nullptr;
     int32_t *h_ndets = nullptr, *h_nprops = nullptr;
@@ -249,13 +250,14 @@ int pp_detector_create(pp_net* netA, pp_net* netB, const int32_t* bufs_a, const 
     d->kflag1 = (unsigned char*)(base + o_k1); d->kflag2 = (unsigned char*)(base + o_kf2);
     d->reg_rois = (float*)(base + o_rr); d->reg_boxes = (float*)(base + o_rb); d->reg_scores = (float*)(base + o_rsc);
     d->reg_n = (int32_t*)(base + o_rn); d->reg_n_out = (int32_t*)(base + o_rno);
-    d->h_margins.assign((size_t)F * PP_DET_N_MARGINS, 0.f);
     for (auto& e : d->ev) PP_HIP_CHECK(hipEventCreate(&e));
     PP_HIP_CHECK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
     PP_HIP_CHECK(hipHostMalloc((void**)&d->h_dets, (size_t)F * d->max_det * 5 * sizeof(float)));
     PP_HIP_CHECK(hipHostMalloc((void**)&d->h_ndets, (size_t)F * sizeof(int32_t)));
     PP_HIP_CHECK(hipHostMalloc((void**)&d->h_props, (size_t)F * d->max_rois * 16));
     PP_HIP_CHECK(hipHostMalloc((void**)&d->h_nprops, (size_t)F * sizeof(int32_t)));
+    PP_HIP_CHECK(hipHostMalloc((void**)&d->h_margins, (size_t)F * PP_DET_N_MARGINS * sizeof(float)));
+    memset(d->h_margins, 0, (size_t)F * PP_DET_N_MARGINS * sizeof(float));
     PP_HIP_CHECK(hipStreamSynchronize(s));
     *out = d.release();
     return PP_OK;
@@ -269,7 +271,7 @@ void pp_detector_destroy(pp_detector* d) {
     for (auto& e : d->ev)
         if (e) (void)hipEventDestroy(e);
     if (d->ev_done) (void)hipEventDestroy(d->ev_done);
-    for (void* p : {(void*)d->h_dets, (void*)d->h_ndets, (void*)d->h_props, (void*)d->h_nprops})
+    for (void* p : {(void*)d->h_dets, (void*)d->h_ndets, (void*)d->h_props, (void*)d->h_nprops, (void*)d->h_margins})
         if (p) (void)hipHostFree(p);
     delete d;
 }
@@ -391,10 +393,12 @@ int pp_detector_enqueue(pp_detector* d, const uint8_t* frames, int n_frames, int
     rc = det_enqueue_gather(s, d->fin_boxes, d->fin_scores, d->max_rois, d->keep2, d->n_keep2, d->max_det, d->out_dets, nullptr, d->n_out, 1, F,
                             mcol(PP_DET_MARGIN_DET_TOP), mcol(PP_DET_MARGIN_DET_ORDER), MS);
     if (rc != PP_OK) return rc;
+    // the staging buffer is being overwritten from here on: what it held is gone, and what it will hold is published at collect
     d->h_margins_frames = 0;
+    d->pending_margins = 0;
     if (mg) {
-        PP_HIP_CHECK(hipMemcpyAsync(d->h_margins.data(), mg, (size_t)F * MS * sizeof(float), hipMemcpyDeviceToHost, s));
-        d->h_margins_frames = F;
+        PP_HIP_CHECK(hipMemcpyAsync(d->h_margins, mg, (size_t)F * MS * sizeof(float), hipMemcpyDeviceToHost, s));
+        d->pending_margins = F;
     }
     PP_HIP_CHECK(hipEventRecord(d->ev[6], s));
     PP_HIP_CHECK(hipMemcpyAsync(dets, d->out_dets, (size_t)F * d->max_det * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -415,6 +419,8 @@ int pp_detector_collect(pp_detector* d, float* dets, int32_t* n_dets, float* pro
     PP_HIP_CHECK(hipEventSynchronize(d->ev_done));
     d->pending_frames = 0;
     d->resident_frames = F;
+    d->h_margins_frames = d->pending_margins;     // complete now: ev_done was recorded after the margins' copy
+    d->pending_margins = 0;
     memcpy(dets, d->h_dets, (size_t)F * d->max_det * 5 * sizeof(float));
     memcpy(n_dets, d->h_ndets, (size_t)F * sizeof(int32_t));
     if (proposals) memcpy(proposals, d->h_props, (size_t)F * d->max_rois * 16);
@@ -491,14 +497,16 @@ int pp_detector_enable_margins(pp_detector* d, int enable, float score_weight) {
     d->margins_on = enable != 0;
     d->score_weight = score_weight;
     d->h_margins_frames = 0;
+    d->pending_margins = 0;      // (a pass in flight was enqueued under the old setting: its margins are not published)
     return PP_OK;
 }
 
 int pp_detector_margins(pp_detector* d, int n_frames, float* margins) {
     PP_REQUIRE(d && margins, "pp_detector_margins: NULL argument");
     PP_REQUIRE(d->margins_on, "pp_detector_margins: margins are not enabled (pp_detector_enable_margins)");
+    PP_REQUIRE(d->pending_frames == 0, "pp_detector_margins: a pass is in flight (collect it first)");
     PP_REQUIRE(n_frames == d->h_margins_frames, "pp_detector_margins: the last run had %d frames, %d asked for", d->h_margins_frames, n_frames);
-    memcpy(margins, d->h_margins.data(), (size_t)n_frames * PP_DET_N_MARGINS * sizeof(float));   // (pp_detector_run synchronised after the copy)
+    memcpy(margins, d->h_margins, (size_t)n_frames * PP_DET_N_MARGINS * sizeof(float));   // (pp_detector_collect waited for the copy)
     return PP_OK;
 }
 

@@ -1035,6 +1035,9 @@ int pp_net_run(pp_net* net, int batch, int first_op, int last_op) {
     PP_REQUIRE(first_op >= 0 && last_op <= (int)net->ops.size() && first_op <= last_op, "pp_net_run: bad op range");
     if (net->graph_exec && batch == net->graph_batch && first_op == 0 && last_op == (int)net->ops.size()) {
         PP_HIP_CHECK(hipGraphLaunch(net->graph_exec, net->ctx->stream));
+        // the replay is the run a pending promise (pp_net_input_amax) covered: whether the graph takes the maxima itself was fixed at
+        // capture, and a promise left standing would make the next eager run skip its maxima pass and scale by stale maxima
+        for (auto& e : net->ext) e.provided = false;
         return PP_OK;
     }
     hipStream_t main = net->ctx->stream;
