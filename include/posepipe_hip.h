@@ -312,7 +312,7 @@ int pp_net_capture(pp_net* net, int batch);
 /* per-op elapsed time of the last profiled run (HIP events around each op), ms; NULL-safe */
 int pp_net_profile(pp_net* net, int batch, float* ms_per_op);
 /* which kernel family each op of this net launches (fixed at creation): 0 = not a convolution, 1 = float32 MFMA kernels
- * (conv_igemm*.hip), 2 = bf16-split kernel (conv_split.hip).  kinds: n_ops ints.  (bench.py prices the two families
+ * (conv_igemm*.hip), 2 = bf16-split kernel (conv_split*.hip).  kinds: n_ops ints.  (bench.py prices the two families
  * against their own peaks.) */
 int pp_net_conv_kinds(pp_net* net, int* kinds);
 /* Folded projection shortcuts (fp16-form nets only; fixed at creation).  A 1x1 convolution A (any stride; no activation, no

@@ -7,7 +7,7 @@
 #include "pp_internal.h"
 
 #include <atomic>
-extern std::atomic<int> g_decode_generic, g_split_gemm_epi;      // dark_decode.hip, conv_split.hip
+extern std::atomic<int> g_decode_generic, g_split_gemm_epi;      // dark_decode.hip, conv_split_gemm.hip
 
 static thread_local std::string g_last_error;
 

@@ -14,7 +14,7 @@ struct pp_net {
     std::vector<size_t> buf_elems;  // per-sample floats
     float* weights = nullptr;
     size_t n_weights = 0;
-    // conv_split.hip: the eligible convs' weights as bf16 planes in fragment order (built on the device at creation)
+    // conv_split_weights.hip: the eligible convs' weights as bf16 planes in fragment order (built on the device at creation)
     unsigned char* wsplit = nullptr;
     std::vector<SplitPlan> split_plan;   // per op, split nets: how the op runs on the split kernels (SPLIT_NONE: the fp32-MFMA kernels)
     int numerics = PP_NET_NUMERICS_EXACT;   // fixed at creation (ABI 7)

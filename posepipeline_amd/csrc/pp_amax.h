@@ -1,6 +1,6 @@
 // Per-sample running maximum of |activation| (device helpers) -- what the fp16 form of the split convolutions scales its input by.
 //
-// conv_split.hip (round 5): x s = h0 + 2^-11 h1 holds 22 significand bits wherever |x s| is a NORMAL float16, so the scale s has to
+// conv_split.hip (design narrative, round 5; the kernels are in conv_split_*.hip): x s = h0 + 2^-11 h1 holds 22 significand bits wherever |x s| is a NORMAL float16, so the scale s has to
 // follow the data: s = 2^k PER SAMPLE with max |x| s in [2^14, 2^15).  A per-sample (not per-batch) scale keeps a frame's result
 // independent of what else is in the batch (tests/test_gpu_sharded.py compares shards with the whole clip bit for bit).  The maximum
 // is tracked where the tensor is PRODUCED: every kernel that stores a tensor a fp16-form convolution reads folds max |v| of what it

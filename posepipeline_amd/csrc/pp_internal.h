@@ -120,7 +120,7 @@ struct ConvArgs {
     const uint2* tap_table;
     int x_pad, y_pad, r1_pad, r2_pad;   // zero halo (right columns / bottom rows) of the input, output and residual buffers (pp_buf.pad)
     int no_bounds;          // set by pp_launch_conv: no tap can leave the image (no padding) and the tensor is < 2 GiB
-    // conv_split.hip: the weights pre-split into bf16 planes in fragment order (pp_conv_split_weights); null: pp_launch_conv
+    // conv_split_weights.hip: the weights pre-split into bf16 planes in fragment order (pp_conv_split_weights); null: pp_launch_conv
     // builds a temporary copy when it picks the split kernel (single-op API; never under graph capture)
     const void* wsplit;
     // 0: single-op API -- the process-wide setting (pp_conv_exact) decides; 1 / 2: an op of a net created exact / split (ABI 7: a
@@ -143,7 +143,7 @@ struct ConvArgs {
     const unsigned* x2_amax;
     int Cin2, Hin2, Win2, stride2, x2_pad;
 };
-// ---- fp32 convolution on the bf16 matrix cores (three-way split; conv_split.hip) ----------------------------------------------
+// ---- fp32 convolution on the bf16 matrix cores (three-way split; conv_split.hip: design, plan and dispatch; conv_split_*.hip: one file per kernel family) ------
 // pixel tiling of a split tap kernel: output tiles of TH x TW (MODE_TILE), the padded input as one stream (MODE_STREAM) or 256 output
 // pixels per workgroup (MODE_GEMM); eff: the fraction of a tile's pixels that are outputs (pick_tile / pick_tile_s2), < 0: none fits
 struct TileGeom {

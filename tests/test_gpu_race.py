@@ -1,7 +1,7 @@
 """Race screen for the hand-synchronised kernels of the default numerics.
 
 conv_split_kernel's 8-wave form and conv_split_gemm_kernel issue `global_load_lds_dwordx4` as raw instructions the compiler cannot
-see and order their LDS traffic by COUNTED `s_waitcnt vmcnt(n)` and by barriers placed by hand (csrc/conv_split.hip).  A
+see and order their LDS traffic by COUNTED `s_waitcnt vmcnt(n)` and by barriers placed by hand (csrc/conv_split_*.hip, conv_split_tap.h).  A
 miscounted wait or a missing barrier does not fail deterministically: it shows as an occasional wrong tile when the memory
 system is busy.  So every such form -- 8-wave tile and stream forms, the 4-wave ring form (RING4), COB 1 and 2, even and odd chunk
 counts, conv_split_gemm_kernel<2,4> / <4,2> / <2,2> -- is launched 50 times inside layer programs that run on 4 HIP streams (the forms

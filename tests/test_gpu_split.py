@@ -1,4 +1,4 @@
-"""The library's default convolution numerics: float32 convolutions on the bf16 / fp16 matrix cores (conv_split.hip).
+"""The library's default convolution numerics: float32 convolutions on the bf16 / fp16 matrix cores (conv_split*.hip).
 
 Two forms.  bf16: every float32 operand is split exactly into three bfloat16 values and six of the nine partial products are
 accumulated in float32; the dropped terms are <= 2^-23 of a product.  fp16 (round 5, the default): two float16 terms per operand

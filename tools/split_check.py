@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""bf16-split convolution (conv_split.hip) against the exact fp32 kernel and a float64 convolution: error of both."""
+"""bf16-split convolution (conv_split*.hip) against the exact fp32 kernel and a float64 convolution: error of both."""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Reads the per-workgroup timeline a -DPP_SPLIT_TIMELINE build of conv_split.hip appends to $POSEPIPE_SPLIT_TIMELINE and prints, per
+"""Reads the per-workgroup timeline a -DPP_SPLIT_TIMELINE build of the conv_split*.hip files (tools/build_variant.sh) appends to $POSEPIPE_SPLIT_TIMELINE and prints, per
 layer class (kernel form, map, channels): where a workgroup's time goes (s_memtime ticks = shader cycles: index set-up, first patch,
 rest of the prologue, K loop, epilogue until the loads are consumed, stores issued, stores acknowledged) and how well the resident
 workgroups of a CU cover each other (fraction of the launch during which >= 1 / >= 2 of a CU's workgroups are inside their K loop).
