@@ -686,6 +686,33 @@ int pp_videopose3d_lift_many(pp_net* net, int in_buf, int out_buf, const float* 
 int pp_videopose3d_lift(pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, int n_frames,
                         int in_features, int out_features, int pad, float* out);
 
+/* pp_gastnet_lift_many: the chunk loop, flip test-time augmentation and camera rotation of the GAST-Net lifter
+ * (posepipeline_amd/wrappers/gastnet.py: lift_chunks, camera_to_world) for n_seg tracks in one call (gastnet.hip).
+ *   net        a program of posepipeline_amd.models.gastnet.  in_buf is its [17][T + 2*pad][4] input, out_buf its
+ *              [17][T][3] output; T is read from the buffers.  Any other shape: PP_ERR_ARG.
+ *   kpts_norm  packed [sum seg_len[i]][17][2] fp32, segment after segment: the screen-normalised H36M joints of
+ *              each track's VALID frames (invalid frames are dropped by the caller), 8-byte aligned.
+ *   seg_len    host [n_seg], frames per segment, each >= 1 (a segment of 0 frames: PP_ERR_ARG).
+ *              n_seg == 0: PP_OK, nothing is read, written or queued.
+ *   pad        (receptive field - 1) / 2 of the program.
+ *   flip       != 0: a work item takes TWO batch samples, the window and its mirror image (x negated, left and
+ *              right joints swapped); PP_ERR_ARG on a net with max_batch < 2.  0: one sample, no mirror image.
+ *   cam_quat   host float[4] (w, x, y, z), or NULL: no rotation.
+ *   out        packed [sum seg_len[i]][17][3] fp32 in the same row order; every row is written exactly once.
+ *   mem        PP_MEM_HOST: kpts_norm and out are host arrays, one upload and one download.  PP_MEM_DEVICE: both
+ *              are device arrays that do not overlap; nothing is copied but the work table.
+ *   - A work item is one (segment, chunk of T output frames) pair.  Sample [j][w] of an item holds (x, y, 0, 0)
+ *     of joint j of frame clamp(t0 - pad + w, 0, seg_len - 1) of ITS segment: edge replication at both ends of
+ *     the track, and the last chunk filled up with its last frame.  Items of different segments share a batch, in
+ *     groups of max_batch (/ 2 with flip) items; what a sample holds does not depend on the grouping.
+ *   - For the first min(T, seg_len - t0) frames of an item: m = (y0 + mirror(y1)) / 2 (flip; else m = y0), then
+ *     m + 2 (q_w (q x m) + q x (q x m)) (cam_quat; else m), every step one rounded float32 operation in the order
+ *     of the host formulas: segment i of `out` equals camera_to_world(GastNetLifter.lift(segment i)) bit for bit.
+ *   - The input's per-sample maxima (fp16-form convolutions) are taken by the net itself: no promise is made.
+ *   - Everything is queued on the context's stream; ONE stream synchronisation; results are complete on return. */
+int pp_gastnet_lift_many(pp_net* net, int in_buf, int out_buf, const float* kpts_norm, const int32_t* seg_len,
+                         int n_seg, int pad, int flip, const float* cam_quat, float* out, int mem);
+
 /* ---- bottom-up stage (crop_affine.hip, bottomup.hip) -------------------------------------------------
  * HigherHRNet + associative embedding as mmpose 0.x runs it for `mmpose_bottom_up` (wrappers/mmpose.py:84-121; test_cfg of
  * 3rdparty/mmpose/config/bottom_up/higherhrnet/coco/higher_hrnet48_coco_512x512.py).  mmpose is not vendored: the rules below

@@ -155,6 +155,7 @@ SIGNATURES = {
     "pp_nms": (_i, [_vp, _vp, _vp, _i, C.c_double, _i, _vp, C.POINTER(C.c_int32), _i]),
     "pp_videopose3d_lift": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "pp_videopose3d_lift_many": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i]),
+    "pp_gastnet_lift_many": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     "pp_letterbox_bicubic": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "pp_yolo_decode": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
     "pp_reid_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),

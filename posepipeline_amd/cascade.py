@@ -13,6 +13,10 @@ stores for `keep_tracks = [tid]` -- PersonBbox's bfill / ffill(limit 2), zero ro
 over the window [t-121, t+121] of the WHOLE clip -- with the latency those look-aheads need: the crops of frames whose
 box is back-filled from the next chunk come from a 2-frame tail buffer kept on the device, frame t is lifted once frame
 t+121 has its key points, `flush()` emits the rest at the end of the clip.
+
+`Cascade(lifter="GastNet")` lifts with GAST-Net instead, the reference's default lifting method, which completes its default
+recipe (DeepSortYOLOv4 -> MMPose -> GastNet) as one stream: the invalid frames of a track are dropped and the compacted sequence of
+valid ones is lifted (person_stream.py), a valid frame once 13 further valid frames of its track have their key points.
 """
 from __future__ import annotations
 
@@ -40,6 +44,14 @@ CERTIFY_EPS = {"rpn_cut": 2e-5, "rpn_nms": 5e-5, "rpn_top": 2e-5, "roi_level": 2
                "det_top": 5e-5, "det_order": 4e-5, "trk_score": 2e-5}
 
 
+# Cascade(lifter="GastNet"): output frames per invocation of the lifting program.  A step hands over, per person, its new valid
+# frames and their halo (chunk + 2 x 13 frames); the program's batch has room for the k = ceil of that / GAST_CHUNK work items of
+# every person, each a chunk and its mirror image.
+# Measured (tools/gastnet_timing.py --persons 4 --step 8, DESIGN_LOG.md 5v): chunk 16 is the fastest of 8 / 16 / 32 / 64 in both
+# numerics (1.46 ms per call in split numerics; 8: 1.50, 64: 1.64, 32: 1.72).
+GAST_CHUNK = 16
+
+
 # HIP streams ("lanes") per program inside a cascade.  Filled in from the same-box A/B of round 6 (profiles/r06_lanes_ab.txt).
 LANES = {"detector": 2, "pose": 2}
 
@@ -59,7 +71,7 @@ class Cascade:
                  chunk: int = 8, max_persons: int = 1, pose_spec=None, post="unbiased", blur_kernel=17,
                  tracking: str = "MMTrack_deepsort", keep_tracks=None, flip_pairs=None, blob_fn=None, reid_sd=None,
                  overlap_detector: bool | None = None, numerics=None, id_numerics=None, certify_eps=None, det_lanes=None, pose_lanes=None,
-                 batched_lift: bool = True):
+                 batched_lift: bool = True, lifter: str = "VideoPose3D", lift_spec=None):
         """blob_fn(name, program) -> (device pointer, n_floats) or None, name in "det_a", "det_b", "pose", "lift" (called in
         that order): a weight blob that is already resident on the device -- parallel.broadcast_blob_device delivers rank
         0's over RCCL; the *_sd arguments then only define the program structure (ops, buffers, blob offsets).  Not with
@@ -72,7 +84,12 @@ class Cascade:
         (off / stream / pipeline).
         batched_lift: True (default): the lifting ranges of every followed person that become computable in a step go through ONE
         device-side call (pp_videopose3d_lift_many: their chunks share the lifting program's batch); False: one single-track call per
-        person, one after the other.  Results are bit-equal (a batch sample holds the same values either way)."""
+        person, one after the other.  Results are bit-equal (a batch sample holds the same values either way).
+        lifter: "VideoPose3D" (default) or "GastNet".  With "GastNet", lift_sd is the GAST-Net state dict and lift_spec an optional
+        models.gastnet.GastNetSpec (default: the rf = 27 model in chunks of GAST_CHUNK output frames); the lifting net is a
+        wrappers.gastnet.GastNetLifter on this cascade's context, 2 x max_persons x k samples wide (a chunk and its mirror image per
+        work item, k = ceil((chunk + 2 pad) / lift_spec.chunk) work items per person and step), and every step's ranges go through ONE pp_gastnet_lift_many call (batched_lift=False: one call
+        per person).  Steps emit `keypoints_valid` beside `keypoints_3d` (person_stream.py)."""
         # numerics: "exact" / "split" / None (= the process default at this moment) for EVERY program this cascade creates, passed
         # down explicitly -- two threads building cascades in different modes do not interfere (unlike _lib.default_numerics).
         # id_numerics (round 5): numerics of the programs whose outputs feed INTEGER decisions -- the detector (top-k, NMS, score
@@ -84,6 +101,10 @@ class Cascade:
         # a frame whose every margin clears `certify_eps` keeps its fast detections, the others are run again through a float32-MFMA
         # detector (bit-identical to the oracle).  Which frames were certified is reported per step (`certified`), the policy below
         # falls back to the exact detector alone while fewer than half of a chunk's frames certify.
+        if lifter not in ("VideoPose3D", "GastNet"):
+            raise ValueError(f"Cascade: lifter = {lifter!r}, expected 'VideoPose3D' or 'GastNet'")
+        if lift_spec is not None and lifter != "GastNet":
+            raise ValueError("Cascade: lift_spec goes with lifter='GastNet'")
         self.certified = id_numerics == "certified"
         if self.certified:
             assert tracking == "MMTrack_deepsort" and reid_sd is None, "certified ids: the Faster-RCNN + SORT configuration"
@@ -154,9 +175,20 @@ class Cascade:
             flip_pairs = {17: hrnet.COCO_FLIP_PAIRS, 133: hrnet.WHOLEBODY_FLIP_PAIRS, 136: hrnet.HALPE_FLIP_PAIRS}[self.k]
         self.topdown = ops.TopDown(self.pose_net, self.k, flip_perm=hrnet.flip_perm(self.k, flip_pairs), shift_heatmap=shift,
                                    post=post, blur_kernel=blur_kernel)
-        self.lift_spec = vp3d.VideoPose3DSpec()
-        lift_prog = vp3d.build_videopose3d_program(self.lift_spec, lift_sd)
-        self.lift_net = Net(ctx, lift_prog, max_batch=max(1, max_persons), blob_dev=blob_fn("lift", lift_prog), numerics=numerics)
+        self.lifter = lifter
+        self.gast = None
+        if lifter == "GastNet":
+            from .models import gastnet as gn
+            from .wrappers.gastnet import GastNetLifter
+            self.lift_spec = gn.GastNetSpec(chunk=GAST_CHUNK) if lift_spec is None else lift_spec
+            k_items = -(-(chunk + 2 * self.lift_spec.pad) // self.lift_spec.chunk)
+            self.gast = GastNetLifter(ctx=ctx, numerics=numerics, state_dict=lift_sd, spec=self.lift_spec, flip_augment=True,
+                                      max_batch=2 * max(1, max_persons) * k_items, blob_fn=lambda prog: blob_fn("lift", prog))
+            self.lift_net = self.gast.net
+        else:
+            self.lift_spec = vp3d.VideoPose3DSpec()
+            lift_prog = vp3d.build_videopose3d_program(self.lift_spec, lift_sd)
+            self.lift_net = Net(ctx, lift_prog, max_batch=max(1, max_persons), blob_dev=blob_fn("lift", lift_prog), numerics=numerics)
         # lanes per program (pp_net_set_lane_count; results identical for any count): measured round 6 on the 1080p cascade, see LANES
         env_det, env_pose = os.environ.get("POSEPIPE_DET_LANES"), os.environ.get("POSEPIPE_POSE_LANES")
         det_lanes = int(env_det) if env_det else (LANES["detector"] if det_lanes is None else det_lanes)
@@ -199,6 +231,9 @@ class Cascade:
             for net in (getattr(det, "net_a", None), getattr(det, "net_b", None)):
                 if net is not None:
                     net.close()
+        if getattr(self, "gast", None) is not None:
+            self.gast.close()             # its net is lift_net; the context stays the caller's
+            self.gast, self.lift_net = None, None
         for name in ("pose_net", "lift_net"):
             net = getattr(self, name, None)
             if net is not None:
@@ -222,6 +257,12 @@ class Cascade:
             self.tracker = SortReidTracker()
         else:
             self.tracker = Tracker(mode=1, match_iou_thr=0.5, obj_score_thr=self.tracker_score_thr)
+        if self.gast is not None:     # GAST-Net: the stream hands over compacted, converted (n, 17, 2) rows (person_stream.py)
+            self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs,
+                                         lambda x: self.gast.lift_many([x])[0], max_persons=self.max_persons,
+                                         keep_tracks=self.keep_tracks, lift_many_fn=self.gast.lift_many if self.batched_lift else None,
+                                         lifter="GastNet")
+            return
         # the lifting network takes the 17 COCO joints; wider heads (Halpe-136 / WholeBody-133) start with them
         self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs,
                                      lambda kn: lift(self.lift_net, self.lift_spec, kn[:, :17]),
@@ -237,9 +278,11 @@ class Cascade:
 
     @property
     def flops_per_frame(self):
-        """algorithmic conv FLOPs per frame at max_persons persons (detector + 2 x HRNet per person + lifting)"""
+        """algorithmic conv FLOPs per frame at max_persons persons (detector + 2 x HRNet per person + lifting; GAST-Net: both samples
+        of a chunk, the window and its mirror image)"""
+        samples = 2 if self.gast is not None else 1
         return (self.detector.flops_per_frame + 2 * self.max_persons * self.pose_net.prog.flops +
-                self.max_persons * self.lift_net.prog.flops / self.lift_spec.chunk)
+                samples * self.max_persons * self.lift_net.prog.flops / self.lift_spec.chunk)
 
     # ---- stage 1: detect + associate ------------------------------------------------------------------------
     @staticmethod

@@ -4,9 +4,15 @@
 //   PP_OP_GRAPH_MIX    channel-wise graph convolution (SemCHGraphConv with the softmaxed adjacency, and the BatchNorm behind it, folded
 //                      into a per-channel 17 x 17 matrix on the host), g graphs in one pass
 //   PP_OP_JOINT_ATTN   per time step and head, softmax(q k^T) v over the 17 joints (MultiGlobalGraph), no scale
-// Both are float32 on the vector ALU and memory bound: every input element is read from global memory once, every output written
+// and pp_gastnet_lift_many (at the end of the file): the lifter's chunk loop for every track of a call, windows, mirror images, flip
+// merge and camera rotation as two kernels around the program.
+// Both ops are float32 on the vector ALU and memory bound: every input element is read from global memory once, every output written
 // once.  exp is evaluated in double and rounded once (the header's convention).  No atomics: every sum has one fixed order.
 #include "pp_internal.h"
+
+#include <algorithm>
+#include <climits>
+#include <vector>
 
 namespace {
 
@@ -199,5 +205,178 @@ int pp_launch_joint_attn(const float* qkv, float* out, int n, int h, int w, int 
     hipLaunchKernelGGL(joint_attn_kernel, dim3((unsigned)blocks, (unsigned)n), dim3(64 * waves), lds, stream, qkv, out, w, heads, hd,
                        c_real, c_buf, y_stride, y_coff);
     PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+// ---- pp_gastnet_lift_many ----------------------------------------------------------------------------------------------------------
+// The chunk loop of wrappers/gastnet.lift_chunks for every track of a call, on the device (the shape of lifting.hip): a work item is
+// one (segment, chunk of T output frames) pair; with flip it takes two batch samples, the window and its mirror image, next to each
+// other.  gast_pack_kernel writes the samples of one batch group from the packed tracks, the program runs, gast_merge_kernel averages
+// each pair, rotates into world space and scatters the item's frames into the packed result.  One upload of tracks and work table,
+// one download, one synchronisation per call.  Every float32 operation of the merge is one rounded product, sum or difference in the
+// order of the host formula (wrappers/gastnet.lift_chunks, camera_to_world): the result is the host's, bit for bit.
+int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
+int pp_net_max_batch(pp_net* net);
+pp_ctx* pp_net_ctx(pp_net* net);
+void pp_net_void_input_amax(pp_net* net, int buf);
+
+namespace {
+
+// per work item: first row of its segment in the packed arrays, rows of the segment, first output frame of the chunk
+struct GastItem {
+    int32_t base, len, t0;
+};
+
+struct GastQuat {
+    float w, x, y, z;
+};
+
+// wrappers/gastnet._MIRROR: the left and right joints of the H36M skeleton swapped (its own inverse)
+__device__ __forceinline__ int gast_mirror(int j) {
+    constexpr int m[GJ] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
+    return m[j];
+}
+
+// in[item * S + s][j][w][0 .. 3] = (x, y, 0, 0) of frame clamp(t0 - pad + w, 0, len - 1) of the item's segment (np.pad 'edge', and the
+// last chunk filled up with its last frame); sample s = 1: joint mirror(j) with x negated.  One thread per float4.
+__global__ __launch_bounds__(256) void gast_pack_kernel(const float2* __restrict__ src, const GastItem* __restrict__ items, int total,
+                                                         int iw, int pad, int S, float4* __restrict__ in) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int w = idx % iw;
+    const int j = (idx / iw) % GJ;
+    const int smp = idx / (iw * GJ);
+    const GastItem it = items[smp / S];
+    const bool mir = (smp % S) != 0;
+    int row = it.t0 - pad + w;
+    row = row < 0 ? 0 : (row >= it.len ? it.len - 1 : row);
+    const float2 v = src[((size_t)it.base + row) * GJ + (mir ? gast_mirror(j) : j)];
+    in[idx] = make_float4(mir ? -v.x : v.x, v.y, 0.f, 0.f);
+}
+
+// np.cross(q, v) in float32: per component two rounded products and one rounded difference
+__device__ __forceinline__ void gast_cross(float qx, float qy, float qz, const float* v, float* c) {
+    c[0] = __fsub_rn(__fmul_rn(qy, v[2]), __fmul_rn(qz, v[1]));
+    c[1] = __fsub_rn(__fmul_rn(qz, v[0]), __fmul_rn(qx, v[2]));
+    c[2] = __fsub_rn(__fmul_rn(qx, v[1]), __fmul_rn(qy, v[0]));
+}
+
+// dst[base + t0 + r][j] = rotate((y0[j][r] + mirror(y1)[j][r]) / 2) for r < min(T, len - t0).  One thread per (item, joint, frame).
+__global__ __launch_bounds__(256) void gast_merge_kernel(const float* __restrict__ out, const GastItem* __restrict__ items, int total,
+                                                          int T, int S, int rotate, GastQuat q, float* __restrict__ dst) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int r = idx % T;
+    const int j = (idx / T) % GJ;
+    const int ci = idx / (T * GJ);
+    const GastItem it = items[ci];
+    if (r >= it.len - it.t0) return;
+    const float* y0 = out + (((size_t)ci * S * GJ + j) * T + r) * 3;
+    float v[3] = {y0[0], y0[1], y0[2]};
+    if (S == 2) {
+        const float* y1 = out + ((((size_t)ci * S + 1) * GJ + gast_mirror(j)) * T + r) * 3;
+        v[0] = __fmul_rn(__fadd_rn(v[0], -y1[0]), 0.5f);
+        v[1] = __fmul_rn(__fadd_rn(v[1], y1[1]), 0.5f);
+        v[2] = __fmul_rn(__fadd_rn(v[2], y1[2]), 0.5f);
+    }
+    if (rotate) {
+        float uv[3], uuv[3];
+        gast_cross(q.x, q.y, q.z, v, uv);
+        gast_cross(q.x, q.y, q.z, uv, uuv);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = __fadd_rn(v[k], __fmul_rn(2.f, __fadd_rn(__fmul_rn(q.w, uv[k]), uuv[k])));
+    }
+    float* d = dst + (((size_t)it.base + it.t0 + r) * GJ + j) * 3;
+    d[0] = v[0];
+    d[1] = v[1];
+    d[2] = v[2];
+}
+
+// everything of one call up to, not including, the final synchronisation; `items` must outlive that synchronisation
+int gast_lift_many_enqueue(pp_net* net, pp_ctx* ctx, int in_buf, int out_buf, const float* kpts_norm, const std::vector<GastItem>& items,
+                           size_t rows, int pad, int iw, int T, int S, const float* cam_quat, float* out, int mem) {
+    hipStream_t s = ctx->stream;
+    const int per_group = pp_net_max_batch(net) / S;          // items per batch group
+    const bool host = mem == PP_MEM_HOST;
+    const size_t in_e = rows * GJ * 2, out_e = rows * GJ * 3;
+    int rc = ctx->ensure_scratch(ScratchCursor::align(items.size() * sizeof(GastItem)) +
+                                 (host ? ScratchCursor::align(in_e * sizeof(float)) + ScratchCursor::align(out_e * sizeof(float)) : 0));
+    if (rc != PP_OK) return rc;
+    ScratchCursor cur(ctx);
+    GastItem* d_items = cur.take<GastItem>(items.size());
+    const float* d_src = kpts_norm;
+    float* d_dst = out;
+    if (host) {
+        float* staged = cur.take<float>(in_e);
+        d_dst = cur.take<float>(out_e);
+        PP_HIP_CHECK(hipMemcpyAsync(staged, kpts_norm, in_e * sizeof(float), hipMemcpyHostToDevice, s));
+        d_src = staged;
+    }
+    PP_REQUIRE((reinterpret_cast<uintptr_t>(d_src) & 7) == 0, "pp_gastnet_lift_many: kpts_norm must be 8-byte aligned");
+    PP_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GastItem), hipMemcpyHostToDevice, s));
+    void *in_ptr = nullptr, *out_ptr = nullptr;
+    rc = pp_net_buffer(net, in_buf, &in_ptr, nullptr);
+    if (rc == PP_OK) rc = pp_net_buffer(net, out_buf, &out_ptr, nullptr);
+    if (rc != PP_OK) return rc;
+    PP_REQUIRE(aligned16(in_ptr), "pp_gastnet_lift_many: the program's input buffer must be 16-byte aligned");
+    GastQuat q{1.f, 0.f, 0.f, 0.f};
+    if (cam_quat) q = GastQuat{cam_quat[0], cam_quat[1], cam_quat[2], cam_quat[3]};
+    const int n_items = (int)items.size();
+    for (int c0 = 0; c0 < n_items; c0 += per_group) {
+        const int b = std::min(per_group, n_items - c0);
+        int total = b * S * GJ * iw;
+        hipLaunchKernelGGL(gast_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(d_src),
+                           d_items + c0, total, iw, pad, S, static_cast<float4*>(in_ptr));
+        PP_HIP_CHECK(hipGetLastError());
+        pp_net_void_input_amax(net, in_buf);      // the input was just overwritten here, not by pp_net_forward: the net takes its maxima
+        rc = pp_net_run(net, b * S, 0, -1);
+        if (rc != PP_OK) return rc;
+        total = b * GJ * T;
+        hipLaunchKernelGGL(gast_merge_kernel, dim3((total + 255) / 256), dim3(256), 0, s, static_cast<const float*>(out_ptr), d_items + c0,
+                           total, T, S, cam_quat ? 1 : 0, q, d_dst);
+        PP_HIP_CHECK(hipGetLastError());
+    }
+    if (host) PP_HIP_CHECK(hipMemcpyAsync(out, d_dst, out_e * sizeof(float), hipMemcpyDeviceToHost, s));
+    return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_gastnet_lift_many(pp_net* net, int in_buf, int out_buf, const float* kpts_norm, const int32_t* seg_len, int n_seg,
+                                    int pad, int flip, const float* cam_quat, float* out, int mem) {
+    PP_REQUIRE(net, "pp_gastnet_lift_many: NULL net");
+    PP_REQUIRE(n_seg >= 0 && pad >= 0, "pp_gastnet_lift_many: bad dims (n_seg %d, pad %d)", n_seg, pad);
+    PP_REQUIRE(mem == PP_MEM_HOST || mem == PP_MEM_DEVICE, "pp_gastnet_lift_many: mem %d is neither PP_MEM_HOST nor PP_MEM_DEVICE", mem);
+    if (n_seg == 0) return PP_OK;
+    PP_REQUIRE(kpts_norm && seg_len && out, "pp_gastnet_lift_many: NULL argument");
+    size_t rows = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        PP_REQUIRE(seg_len[i] > 0, "pp_gastnet_lift_many: segment %d has %d frames (every segment needs at least one)", i, seg_len[i]);
+        rows += (size_t)seg_len[i];
+    }
+    PP_REQUIRE(rows <= (size_t)INT_MAX / (GJ * 3), "pp_gastnet_lift_many: %zu frames in one call (the work table holds int32 rows)", rows);
+    const int S = flip ? 2 : 1, max_b = pp_net_max_batch(net);
+    PP_REQUIRE(max_b >= S, "pp_gastnet_lift_many: flip needs two samples per work item, the net has max_batch %d", max_b);
+    int ih, iw, ic, oh, ow, oc;
+    PP_REQUIRE(pp_net_dims(net, in_buf, &ih, &iw, &ic) == PP_OK && pp_net_dims(net, out_buf, &oh, &ow, &oc) == PP_OK,
+               "pp_gastnet_lift_many: bad buffer id");
+    PP_REQUIRE(ih == GJ && ic == 4 && oh == GJ && oc == 3 && ow > 0 && iw == ow + 2 * pad,
+               "pp_gastnet_lift_many: program shape (in %dx%dx%d, out %dx%dx%d) is not [17][T + 2 pad][4] -> [17][T][3] at pad=%d",
+               ih, iw, ic, oh, ow, oc, pad);
+    const int T = ow;
+    PP_REQUIRE((size_t)max_b * GJ * iw <= (size_t)INT_MAX, "pp_gastnet_lift_many: batch of %d samples of %d time steps is too large", max_b, iw);
+    std::vector<GastItem> items;                  // one per (segment, chunk), segment after segment
+    int32_t base = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        for (int32_t t0 = 0; t0 < seg_len[i]; t0 += T) items.push_back({base, seg_len[i], t0});
+        base += seg_len[i];
+    }
+    pp_ctx* ctx = pp_net_ctx(net);
+    PpRange range("pp_gastnet_lift_many");
+    int rc = gast_lift_many_enqueue(net, ctx, in_buf, out_buf, kpts_norm, items, rows, pad, iw, T, S, cam_quat, out, mem);
+    // one synchronisation per call, also after an error: `items` and the caller's host arrays are read by queued copies
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc != PP_OK) return rc;
+    PP_HIP_CHECK(e);
     return PP_OK;
 }

@@ -27,6 +27,30 @@ The compute stages are callables, so this module needs no GPU (tests/test_person
     lift_fn(kn)       kn = (n, K, 2) normalised key points -> (n, J, 3)
     lift_many_fn(kns) optional: kns = list of such contexts -> list of (n_i, J, 3), element i equal to lift_fn(kns[i]); when given,
                       advance() makes ONE call with the contexts of every stream instead of one lift_fn call per stream
+
+`PersonStreams(lifter="GastNet")` streams the reference's DEFAULT lifting method instead (LiftingMethodLookup row 0,
+wrappers/gastnet.process_gastnet), whose temporal rule is another one: GAST-Net drops the invalid frames of a track and lifts the
+COMPACTED sequence of the valid ones, where VideoPose3D keeps zero rows in place.
+
+  * Per frame: every decided 2D row (a zero row where the box stayed NaN; the first 17 joints of a wider head) goes, on its own,
+    through the H36M conversion of `h36m_coco_format`, `revise_kpts` and `normalize_screen_coordinates` (rounded to float32): the
+    arithmetic of process_gastnet, one frame at a time.  A frame is VALID iff its 34 converted coordinates do not sum to 0.
+  * The lifted sequence is the track's valid frames only, in order; the window of the i-th valid frame is valid frames
+    i - pad .. i + pad, edge-replicated at the two ends of the track's VALID sequence (so a window spans a gap of invalid frames).
+  * Latency: a valid frame is lifted once `pad` further valid frames of its track are decided, or when the stream is final or
+    ended (the same final / ended / cap logic as above).  With pad = 13 that is 13 valid frames, against VideoPose3D's 121 frames.
+  * `keypoints_3d` rows are emitted for consecutive frames, zero rows at the invalid ones; an invalid frame waits for the valid
+    frames before it.  `keypoints_valid` / `keypoints_valid_frames` ({tid: bool array} / the same frame numbers) go alongside.
+  * lift_fn(x) / lift_many_fn(xs): x = (n, 17, 2) float32 consecutive VALID rows -> (n, 17, 3), each output a function of its window
+    of 2 pad + 1 rows, the window edge-replicated at the two ends of x (GastNetLifter.lift_many).  A range of valid frames [a, b) is
+    handed over with its context [a - pad, b + pad) cut to the valid sequence known so far; rows [a, b) of the result are kept: their
+    windows lie inside the context, or end where the track's valid sequence does.  Every range that becomes computable in one
+    advance() goes through ONE lift_many_fn call.
+  * Declared differences to the table chain.  `h36m_coco_format` converts nothing when the coordinates of the WHOLE CLIP sum to
+    exactly 0 (`kp.sum() != 0.0`); a stream never sees the whole clip and applies the per-frame rule only: the two differ only if the
+    whole clip's coordinates cancel to exactly 0.  A track without any valid frame is a ValueError of process_gastnet; a stream emits
+    its zero rows.  The stream converts the float32 rows of the top-down stage; a table that holds the same values as float64 (rows
+    stacked with float64 zero rows) evaluates the five joints the conversion builds in float64 before rounding them to float32.
 """
 from __future__ import annotations
 
@@ -52,6 +76,11 @@ class _PersonStream:
         self.any_absent = self.first > 0         # reference: a zero row makes the clip's key-point array float64
         self.live = True
         self.k = num_joints
+        # lifter="GastNet": the compacted sequence of valid frames
+        self.g_flags: list = []                  # validity of the decided frames from next3d on (not yet emitted)
+        self.g_rows: list = []                   # normalised (17,2) float32 rows of the valid frames a window can still read
+        self.g_base = 0                          # index, in the valid sequence, of g_rows[0]
+        self.g_next = 0                          # index, in the valid sequence, of the next valid frame to lift
 
     def decide(self, n_frames: int, final: bool):
         """Box decisions for frames [next_dec, n_frames) in order, as far as they can be made.  final: nothing will
@@ -95,7 +124,12 @@ class PersonStreams:
     appears while max_persons others are live is never followed); keep_tracks: follow exactly these ids instead."""
 
     def __init__(self, num_joints: int, pad: int, src_hw, topdown_fn, lift_fn, max_persons: int = 1, keep_tracks=None,
-                 lift_many_fn=None):
+                 lift_many_fn=None, lifter: str = "VideoPose3D"):
+        if lifter not in ("VideoPose3D", "GastNet"):
+            raise ValueError(f"PersonStreams: lifter = {lifter!r}, expected 'VideoPose3D' or 'GastNet'")
+        if lifter == "GastNet" and int(num_joints) < 17:
+            raise ValueError(f"PersonStreams: the GAST-Net rule converts the 17 COCO joints; the 2D stage has {num_joints}")
+        self.lifter = lifter
         self.k, self.pad, self.src = int(num_joints), int(pad), tuple(src_hw)
         self.topdown_fn, self.lift_fn, self.lift_many_fn = topdown_fn, lift_fn, lift_many_fn
         self.max_persons = max_persons
@@ -161,10 +195,55 @@ class PersonStreams:
         out = self.lift_fn(self._lift_context(st, lo, hi, n_total))
         return out[pad:pad + hi - lo]
 
+    def _gast_convert(self, st: _PersonStream, n_new: int):
+        """the GAST-Net host chain on the n_new rows decided last, frame by frame: validity flags and the valid rows, normalised"""
+        from .wrappers import gastnet as gw
+        rows = np.stack(st.k2[len(st.k2) - n_new:])
+        kpts, scores = gw.h36m_rows(rows[:, :gw.NUM_JOINTS, :2], rows[:, :gw.NUM_JOINTS, 2])
+        valid = kpts.reshape(-1, 2 * gw.NUM_JOINTS).sum(axis=1) != 0
+        kpts = gw.revise_kpts(kpts, scores, np.flatnonzero(valid))
+        x = gw.normalize_screen_coordinates(kpts[valid], w=int(self.src[1]), h=int(self.src[0])).astype(np.float32)
+        st.g_flags.extend(bool(v) for v in valid)
+        st.g_rows.extend(x)
+
+    def _gast_range(self, st: _PersonStream, bound: int, closed: bool):
+        """What stream `st` can emit now, frames [next3d, next3d + m) with m > 0, or None.  bound: first frame that cannot be emitted
+        yet; closed: no further valid frame will come.  -> (m, validity of the m frames, rows to keep = (offset, count) in the lifted
+        context, context (n, 17, 2) or None when no frame of the range is valid); advances the stream's state."""
+        pad = self.pad
+        n_valid = st.g_base + len(st.g_rows)
+        n_avail = min(len(st.g_flags), bound - st.next3d)
+        a = b = st.g_next
+        m = 0
+        while m < n_avail:
+            if st.g_flags[m]:
+                if not closed and b + pad >= n_valid:
+                    break                            # this valid frame's window is not complete: it, and what follows, waits
+                b += 1
+            m += 1
+        if m == 0:
+            return None
+        mask = np.array(st.g_flags[:m], bool)
+        ctx_rows, lo = None, a
+        if b > a:
+            lo, hi = max(0, a - pad), min(n_valid, b + pad)
+            ctx_rows = np.stack(st.g_rows[lo - st.g_base:hi - st.g_base])
+        del st.g_flags[:m]
+        st.next3d += m
+        st.g_next = b
+        drop = b - pad - st.g_base                   # valid rows no window will read again
+        if drop > 0:
+            del st.g_rows[:drop]
+            st.g_base += drop
+        return m, mask, (a - lo, b - a), ctx_rows
+
     def advance(self, final: bool = False):
         """Decide boxes, run 2D, emit 3D for everything that has become computable.  final: end of clip.
         Returns dict(keypoints / keypoints_frames = {track_id: (n,K,3) / (n,) frame numbers} decided in this call,
-                     keypoints_3d / keypoints_3d_frames = {track_id: (m,J,3) / (m,)} emitted in this call)."""
+                     keypoints_3d / keypoints_3d_frames = {track_id: (m,J,3) / (m,)} emitted in this call;
+                     lifter="GastNet": also keypoints_valid / keypoints_valid_frames = {track_id: (m,) bool / (m,)})."""
+        gast = self.lifter == "GastNet"
+        kpv, gast_jobs = {}, []       # GastNet: (track_id, frames, validity, (offset, count), context) of every range emitted
         n1 = self.n_frames
         jobs, decided = [], {}
         for tid in sorted(self.streams):
@@ -196,6 +275,21 @@ class PersonStreams:
                 kp_frames[tid] = np.array(te, np.int64)
             # ... and is finalised once its last decided row is one of those zero rows
             ended = (not st.live) and st.next_dec > cap
+            if gast:
+                if ts:
+                    self._gast_convert(st, len(ts))
+                got = self._gast_range(st, st.next_dec if cap is None else min(st.next_dec, cap), final or ended)
+                if got is not None:
+                    kp3_frames[tid] = np.arange(st.next3d - got[0], st.next3d, dtype=np.int64)
+                    kpv[tid] = got[1]
+                    gast_jobs.append((tid,) + got)
+                if final or ended:
+                    del self.streams[tid]
+                    self.finished.add(tid)
+                else:
+                    del st.k2[:]                      # the compacted rows are kept instead (g_rows)
+                    st.k2_base = st.next_dec
+                continue
             if final:
                 hi, n_total = st.next_dec if cap is None else min(st.next_dec, cap), n1
             elif ended:
@@ -222,6 +316,21 @@ class PersonStreams:
             assert len(lifted) == len(batched), (len(lifted), len(batched))
             for (tid, n, _), out in zip(batched, lifted):
                 kp3[tid] = out[pad:pad + n]
+        if gast:
+            todo = [j for j in gast_jobs if j[4] is not None]
+            if todo and self.lift_many_fn is not None:
+                lifted = self.lift_many_fn([j[4] for j in todo])
+                assert len(lifted) == len(todo), (len(lifted), len(todo))
+            else:
+                lifted = [self.lift_fn(j[4]) for j in todo]
+            lifted = {j[0]: out for j, out in zip(todo, lifted)}
+            for tid, m, mask, (off, cnt), _ in gast_jobs:
+                out3 = np.zeros((m, 17, 3), np.float32)
+                if cnt:
+                    out3[mask] = np.asarray(lifted[tid])[off:off + cnt]
+                kp3[tid] = out3
+            return dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames,
+                        keypoints_valid=kpv, keypoints_valid_frames={tid: f.copy() for tid, f in kp3_frames.items()})
         return dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames)
 
 

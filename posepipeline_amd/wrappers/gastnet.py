@@ -15,7 +15,10 @@ float64, "keypoints_valid": [bool] * N}`, zeros at the invalid frames.  The refe
                      camera_to_world with the fixed quaternion, t = 0
 
 The network is models/gastnet.py on a resident Net with max_batch = 2 (the clip and its mirror image), run over chunks of
-`spec.chunk` output frames with `pad`-frame halos.
+`spec.chunk` output frames with `pad`-frame halos.  `process_gastnet` and the streamed cascade go through
+`GastNetLifter.lift_many` (pp_gastnet_lift_many, csrc/gastnet.hip): the windows, the mirror images, the flip merge and the camera
+rotation of every track of a call are device kernels, with one upload and one download per call.  `GastNetLifter.lift` /
+`lift_chunks` / `camera_to_world` are the same arithmetic on the host, chunk by chunk: the reference `lift_many` is tested against.
 
 Declared differences:
   * A clip with no valid frame: ValueError (the reference: an AssertionError inside gen_pose).
@@ -67,17 +70,25 @@ def h36m_coco_format(keypoints, scores):
     out = np.zeros(kp.shape, np.float32)
     out_s = np.zeros(sc.shape, np.float32)
     if kp.sum() != 0.0:
-        out = coco_h36m(kp)
-        sc = sc.astype(np.float32)
-        out_s[:, 9] = sc[:, 0]                                        # nose
-        for h, c in _H36M_FROM_COCO.items():
-            out_s[:, h] = sc[:, c]
-        out_s[:, 0] = (sc[:, 11] + sc[:, 12]) / np.float32(2)
-        out_s[:, 8] = (sc[:, 5] + sc[:, 6]) / np.float32(2)
-        out_s[:, 7] = (out_s[:, 0] + out_s[:, 8]) / np.float32(2)
-        out_s[:, 10] = (((sc[:, 1] + sc[:, 2]) + sc[:, 3]) + sc[:, 4]) / np.float32(4)
+        out, out_s = h36m_rows(kp, sc)
     valid = np.where(out.reshape(-1, 2 * NUM_JOINTS).sum(axis=1) != 0)[0]
     return out, out_s, valid
+
+
+def h36m_rows(kp, sc):
+    """The conversion of h36m_coco_format without its clip-wide guard: every frame's result depends on that frame alone (what a
+    stream, which never sees the whole clip, applies frame by frame).  -> ((N, 17, 2) float32, (N, 17) float32)"""
+    out = coco_h36m(kp)
+    out_s = np.zeros(sc.shape, np.float32)
+    sc = sc.astype(np.float32)
+    out_s[:, 9] = sc[:, 0]                                        # nose
+    for h, c in _H36M_FROM_COCO.items():
+        out_s[:, h] = sc[:, c]
+    out_s[:, 0] = (sc[:, 11] + sc[:, 12]) / np.float32(2)
+    out_s[:, 8] = (sc[:, 5] + sc[:, 6]) / np.float32(2)
+    out_s[:, 7] = (out_s[:, 0] + out_s[:, 8]) / np.float32(2)
+    out_s[:, 10] = (((sc[:, 1] + sc[:, 2]) + sc[:, 3]) + sc[:, 4]) / np.float32(4)
+    return out, out_s
 
 
 # the low-score sets among [2, 3, 5, 6] (right knee, right foot, left knee, left foot) that are repaired: set -> (targets, sources)
@@ -155,17 +166,23 @@ def load_state_dict(spec=gn.GastNetSpec(), seed=7) -> dict:
 
 
 class GastNetLifter:
-    """The resident model: the layer program with every parameter in its blob, on one context, two samples wide.
+    """The resident model: the layer program with every parameter in its blob, on one context, `max_batch` samples wide (2: one
+    chunk and its mirror image; `lift_many` fills a wider batch with the chunks of several tracks).
 
-    numerics: as Net's (None: the process default at this moment)."""
+    numerics: as Net's (None: the process default at this moment).  blob_fn(program) -> Net's blob_dev (a weight blob that is already
+    on the device) or None."""
 
-    def __init__(self, device=0, numerics=None, ctx=None, state_dict=None, spec=gn.GastNetSpec(), flip_augment=True):
+    def __init__(self, device=0, numerics=None, ctx=None, state_dict=None, spec=gn.GastNetSpec(), flip_augment=True, max_batch=2,
+                 blob_fn=None):
         self.spec = spec
         self.flip_augment = bool(flip_augment)
+        if max_batch < (2 if self.flip_augment else 1):
+            raise ValueError(f"GastNetLifter: max_batch = {max_batch}; flip augmentation needs two samples per chunk")
         sd = load_state_dict(spec) if state_dict is None else weights.strip_key_prefix(state_dict, "module.")
         self._own_ctx = ctx is None
         self.ctx = _lib.Context(device) if ctx is None else ctx
-        self.net = Net(self.ctx, gn.build_gastnet_program(spec, sd), max_batch=2, numerics=numerics)
+        prog = gn.build_gastnet_program(spec, sd)
+        self.net = Net(self.ctx, prog, max_batch=int(max_batch), numerics=numerics, blob_dev=None if blob_fn is None else blob_fn(prog))
         self.stage_ms = None
 
     def _forward(self, batch, ms):
@@ -196,6 +213,27 @@ class GastNetLifter:
             ms["post"] = (time.perf_counter() - t0) * 1e3 - ms["upload"] - ms["program"]
         self.stage_ms = ms
         return out
+
+    def lift_many(self, xs, rotate=True) -> list:
+        """xs: list of (n_i, 17, 2) normalised H36M key points (each track's valid frames, n_i >= 1) -> list of (n_i, 17, 3) float32, in
+        ONE pp_gastnet_lift_many call: the chunks of every track share the net's batch, windows, mirror images, flip merge and the
+        camera rotation are device kernels, one upload and one download.  Element i equals camera_to_world(self.lift(xs[i])) bit for
+        bit (self.lift(xs[i]) with rotate=False)."""
+        xs = [np.ascontiguousarray(np.asarray(x), dtype=np.float32) for x in xs]
+        for x in xs:
+            _check_input(x)
+        if not xs:
+            return []
+        seg = np.array([x.shape[0] for x in xs], np.int32)
+        packed = np.ascontiguousarray(np.concatenate(xs))
+        out = np.empty((int(seg.sum()), NUM_JOINTS, 3), np.float32)
+        named = self.net.prog.named
+        _lib.check(self.ctx.lib.pp_gastnet_lift_many(self.net.handle, named["input"], named["output"], _lib.ptr(packed), _lib.ptr(seg),
+                                                     len(seg), self.spec.pad, int(self.flip_augment),
+                                                     _lib.ptr(CAMERA_QUATERNION) if rotate else None, _lib.ptr(out), _lib.PP_MEM_HOST),
+                   "pp_gastnet_lift_many")
+        ends = np.cumsum(seg)
+        return [out[e - n:e] for e, n in zip(ends, seg)]
 
     def close(self):
         if getattr(self, "net", None) is not None:
@@ -231,7 +269,12 @@ def process_gastnet(key):
     kpts = revise_kpts(kpts, scores, valid)
 
     x = normalize_screen_coordinates(kpts[valid], w=width, h=height)
-    prediction = camera_to_world(_model().lift(x.astype(np.float32)))     # torch.from_numpy(batch.astype('float32')) rounds to float32
+    x = x.astype(np.float32)                                   # torch.from_numpy(batch.astype('float32')) rounds to float32
+    model = _model()
+    if hasattr(model, "lift_many"):                            # the one-call device path: windows, flip merge and rotation on the GPU
+        prediction = model.lift_many([x])[0]
+    else:                                                      # a model that offers `lift` alone: the same values, rotated on the host
+        prediction = camera_to_world(model.lift(x))
 
     keypoints_3d = np.zeros((keypoints.shape[0], NUM_JOINTS, 3))
     keypoints_3d[valid] = prediction

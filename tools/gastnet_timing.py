@@ -4,7 +4,14 @@
 events around the copies and around the program's launches, summed over the chunks), post is the host's share (download, flip merge;
 wall) -- and `Net.profile` of one chunk by op type, lanes off, so that the two new ops stand beside the convolutions.
 
+With `--persons P --step N` (DESIGN_LOG.md 5q) it times the streamed cascade's lifting step instead: P tracks that each gain N valid
+frames per call, so every call lifts P segments of N + 2 pad frames (the new frames and their halo).  Per chunk length 8 / 16 / 32 / 64
+it prints the milliseconds per call of the one-call device path (`GastNetLifter.lift_many`: pp_gastnet_lift_many) beside the
+per-person host path (`camera_to_world(lift(x))` in a loop over the persons) on the same lifter, in the same run, after checking
+that both give the same bytes.
+
 usage: python tools/gastnet_timing.py [--out FILE] [--frames 1000] [--numerics exact split]     (needs an MI355X; synthetic weights)
+       python tools/gastnet_timing.py --persons 4 --step 8 [--chunks 8 16 32 64] [--reps 20] [--out FILE]
 """
 import argparse
 import json
@@ -23,13 +30,60 @@ from posepipeline_amd.wrappers import gastnet as W                        # noqa
 OP_NAMES = {L.PP_OP_CONV: "conv", L.PP_OP_GRAPH_MIX: "graph_mix", L.PP_OP_JOINT_ATTN: "joint_attn"}
 
 
+def streaming_step(a):
+    """--persons P --step N: ms per call of lift_many against lift in a loop, per chunk length"""
+    from posepipeline_amd.models import gastnet as gn
+    rng = np.random.default_rng(0)
+    rows = []
+    ctx = L.Context(0)
+    for numerics in a.numerics:
+        for chunk in a.chunks:
+            spec = gn.GastNetSpec(chunk=chunk)
+            n = a.step + 2 * spec.pad
+            items = -(-n // chunk)
+            xs = [rng.uniform(-1, 1, (n, 17, 2)).astype(np.float32) for _ in range(a.persons)]
+            lf = W.GastNetLifter(ctx=ctx, numerics=numerics, spec=spec, max_batch=2 * a.persons * items)
+            many = lf.lift_many(xs)                                      # warm-up of both paths, and the same bytes from both
+            loop = [W.camera_to_world(lf.lift(x)) for x in xs]
+            assert all(np.array_equal(m, h) for m, h in zip(many, loop)), "lift_many differs from the host chain"
+            t_many, t_loop = [], []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                lf.lift_many(xs)
+                t_many.append((time.perf_counter() - t0) * 1e3)
+                t0 = time.perf_counter()
+                for x in xs:
+                    W.camera_to_world(lf.lift(x))
+                t_loop.append((time.perf_counter() - t0) * 1e3)
+            rows.append({"lifter": "GastNetLifter rf=27 channels=128", "numerics": lf.net.numerics, "persons": a.persons, "step": a.step,
+                         "frames_per_segment": n, "chunk": chunk, "items_per_person": items, "max_batch": lf.net.max_batch,
+                         "lift_many_ms_per_call": round(float(np.median(t_many)), 3), "lift_many_ms_min": round(min(t_many), 3),
+                         "lift_loop_ms_per_call": round(float(np.median(t_loop)), 3), "lift_loop_ms_min": round(min(t_loop), 3)})
+            print(json.dumps(rows[-1]), flush=True)
+            lf.close()
+    ctx.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--numerics", nargs="+", default=["exact", "split"])
+    ap.add_argument("--persons", type=int, default=None, help="with --step: time the streamed cascade's lifting step")
+    ap.add_argument("--step", type=int, default=None)
+    ap.add_argument("--chunks", type=int, nargs="+", default=[8, 16, 32, 64])
     a = ap.parse_args()
+    if (a.persons is None) != (a.step is None):
+        ap.error("--persons and --step go together")
+    if a.persons is not None:
+        rows = streaming_step(a)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     rng = np.random.default_rng(0)
     x = rng.uniform(-1, 1, (a.frames, 17, 2)).astype(np.float32)
     rows = []
