@@ -971,6 +971,29 @@ int pp_trades_decode(pp_ctx* ctx, const float* hm, const float* reg, const float
 #define PP_OP_GRAPH_MIX 21
 #define PP_OP_JOINT_ATTN 22
 
+/* ---- PoseC3D skeleton action (posec3d.hip; models/posec3d.py, wrappers/mmaction.py) -------------------------------------------------
+ * The device side of the SkeletonAction stage (pose_pipeline/wrappers/mmaction.py) besides the layer programs, which use PP_OP_CONV,
+ * PP_OP_MAXPOOL and PP_OP_AVGPOOL only.  mmaction2 is not vendored: UNPINNED restatements; numpy / torch twins in
+ * tests/posec3d_ref.py.  Added functions only: no op type, sizeof(pp_op) is unchanged and PP_ABI_VERSION stays 10.
+ *
+ * pp_pose_target: GeneratePoseTarget(sigma, use_score, with_kp, double) for one person.  kps: DEVICE float64 [n][K][3] = (x, y, score)
+ *   in map pixels; perm: DEVICE int32 [K], the joint that channel c of a MIRRORED sample shows (left / right swapped); out: DEVICE
+ *   float32 [2 n][h][w][c_pad] NHWC, c_pad % 4 == 0, c_pad >= K.  For sample s < n, (mu_x, mu_y, score) = kps[s][c]; for sample
+ *   s >= n (the mirrored copies: Flip(flip_ratio 1, left_kp, right_kp) of the key points, rendered again), (x0, mu_y, score) =
+ *   kps[s - n][perm[c]] and mu_x = x0 != 0 ? w - x0 : x0 in float64; a perm[c] outside [0, K) reads nothing and leaves the channel
+ *   zeros.  With int() truncating toward zero,
+ *     st_x = max(int(mu_x - 3 sigma), 0), ed_x = min(int(mu_x + 3 sigma) + 1, w), st_y / ed_y likewise with h;
+ *     out[s][y][x][c] = float32(exp(-((x - mu_x)^2 + (y - mu_y)^2) / 2 / sigma^2) * score)   EVALUATED IN DOUBLE AND ROUNDED ONCE
+ *   where st_x <= x < ed_x, st_y <= y < ed_y and not score < 1e-4; 0 elsewhere and in the channels [K, c_pad).  One person: a
+ *   channel holds one patch, so the reference's np.maximum is a plain store and every element is written exactly once (no memset, no
+ *   scatter, no atomics).  Queued on the ctx stream; no synchronisation.
+ *
+ * pp_gather_samples: dst[i] = src[idx[i]], i < n, whole samples of sample_floats floats (a multiple of 4; float4 copies; src and dst
+ *   16-byte aligned, not overlapping).  idx: DEVICE int32 [n] with values in [0, n_src); a value outside that range reads nothing and
+ *   fills its sample with zeros.  n <= 65535.  Queued on the ctx stream; no synchronisation. */
+int pp_pose_target(pp_ctx* ctx, const double* kps, int n, int K, int h, int w, double sigma, const int32_t* perm, int c_pad, float* out);
+int pp_gather_samples(pp_ctx* ctx, const float* src, int n_src, const int32_t* idx, int n, long long sample_floats, float* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ The reference's make() methods import the wrappers by these paths (pose_pipeline
 pose_pipeline.wrappers.mmtrack import mmtrack_bounding_boxes`, :1020-1039 `...wrappers.mmpose import
 mmpose_top_down_person`, :1270-1273 `...wrappers.videopose3d import process_videopose3d`, :519-523
 `...wrappers.deep_sort_yolov4.parser import tracking_bounding_boxes`, :2012-2018 `...wrappers.hand_bbox`, :2124-2139
-`...wrappers.hand_estimation`, :1561 `...wrappers.vibe`), and scripts use `from pose_pipeline import *` and
+`...wrappers.hand_estimation`, :1561 `...wrappers.vibe`, :1162 `...wrappers.mmaction`), and scripts use `from pose_pipeline import *` and
 `pose_pipeline.utils.standard_pipelines`.  Putting this directory (the repository root) on sys.path BEFORE a reference
 checkout makes every one of those imports land on the drop-in, with no edit to the caller.
 Each sub-module below replaces itself in sys.modules with the posepipeline_amd module of the same role, so
@@ -18,8 +18,8 @@ from posepipeline_amd.pipeline import (BestDetectedFrames, BottomUpMethod, Botto
                                        BottomUpPerson, DetectedFrames, HandBbox, HandBboxMethod,  # noqa: F401
                                        HandBboxMethodLookup, HandPoseEstimation, HandPoseEstimationMethod,
                                        HandPoseEstimationMethodLookup, LiftingMethod, LiftingMethodLookup,
-                                       LiftingPerson, PersonBbox, PersonBboxValid, SMPLMethod, SMPLMethodLookup, SMPLPerson,
-                                       TopDownMethod, TopDownMethodLookup, TopDownPerson, TrackingBbox, TrackingBboxMethod,
+                                       LiftingPerson, PersonBbox, PersonBboxValid, SkeletonAction, SMPLMethod, SMPLMethodLookup,
+                                       SMPLPerson, TopDownMethod, TopDownMethodLookup, TopDownPerson, TrackingBbox, TrackingBboxMethod,
                                        TrackingBboxMethodLookup, Video, VideoInfo)
 from posepipeline_amd.weights import model_data_dir as _model_data_dir
 
@@ -32,7 +32,7 @@ from posepipeline_amd.env import (add_path, pytorch_memory_limit, set_environmen
 MODEL_DATA_DIR = _model_data_dir()
 
 __all__ = ["Video", "VideoInfo", "TrackingBboxMethodLookup", "TrackingBboxMethod", "TrackingBbox", "PersonBboxValid",
-           "PersonBbox", "DetectedFrames", "BestDetectedFrames", "TopDownMethodLookup", "TopDownMethod", "TopDownPerson", "LiftingMethodLookup",
+           "PersonBbox", "DetectedFrames", "BestDetectedFrames", "TopDownMethodLookup", "TopDownMethod", "TopDownPerson", "SkeletonAction", "LiftingMethodLookup",
            "LiftingMethod", "LiftingPerson", "HandBboxMethodLookup", "HandBboxMethod", "HandBbox", "HandPoseEstimationMethodLookup",
            "HandPoseEstimationMethod", "HandPoseEstimation", "BottomUpMethodLookup", "BottomUpMethod", "BottomUpPeople",
            "BottomUpPerson", "SMPLMethodLookup", "SMPLMethod", "SMPLPerson", "MODEL_DATA_DIR", "add_path", "set_environmental_variables",

@@ -196,6 +196,8 @@ SIGNATURES = {
     "pp_smpl_model_destroy": (None, [_vp]),
     "pp_smpl_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "pp_vibe_head_unpack": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "pp_pose_target": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp]),
+    "pp_gather_samples": (_i, [_vp, _vp, _i, _vp, _i, C.c_longlong, _vp]),
 }
 
 _lib = None

@@ -372,6 +372,28 @@ class TopDownPerson(dj.Computed):  # pipeline.py:1011-1015
 
 
 @schema
+class SkeletonAction(dj.Computed):  # pipeline.py:1145-1156
+    definition = """
+    -> TopDownPerson
+    method            : varchar(50)
+    ---
+    top5              : longblob
+    action_scores     : longblob
+    label_map         : longblob
+    action_window_len : int
+    stride            : int
+    computed_timestamp=CURRENT_TIMESTAMP : timestamp    # automatic timestamp
+    """
+
+    def make(self, key):  # pipeline.py:1160-1166
+        from .wrappers.mmaction import mmaction_skeleton_action_person
+
+        key = mmaction_skeleton_action_person(key, stride=1)
+        key["method"] = "mmaction_skeleton"
+        self.insert1(key)
+
+
+@schema
 class LiftingMethodLookup(dj.Lookup):  # pipeline.py:1226-1239
     definition = """
     lifting_method      : int
