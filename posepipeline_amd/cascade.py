@@ -29,11 +29,10 @@ from . import ops
 from .models import faster_rcnn as fr
 from .models import hrnet
 from .models import vitpose
-from .models import videopose3d as vp3d
 from .person_stream import FILL_LIMIT, PersonStreams, collect  # noqa: F401  (collect: re-exported for callers)
 from .program import Net
 from .tracking import Tracker
-from .wrappers.videopose3d import lift, lift_many
+from .wrappers.videopose3d import VideoPose3DLifter
 
 
 # Default certification thresholds of Cascade(id_numerics="certified"): 4x the largest deviation between the fp16-form and the
@@ -83,8 +82,8 @@ class Cascade:
         tensor of the CURRENT chunk) nor with certified ids (synchronous passes).  POSEPIPE_OVERLAP_DETECTOR=0 / 1 / 3 overrides
         (off / stream / pipeline).
         batched_lift: True (default): the lifting ranges of every followed person that become computable in a step go through ONE
-        device-side call (pp_videopose3d_lift_many: their chunks share the lifting program's batch); False: one single-track call per
-        person, one after the other.  Results are bit-equal (a batch sample holds the same values either way).
+        device-side call (pp_videopose3d_lift_many: their chunks share the lifting program's batch); False: one such call per
+        person with that person's track alone, one after the other.  Results are bit-equal (a batch sample holds the same values either way).
         lifter: "VideoPose3D" (default) or "GastNet".  With "GastNet", lift_sd is the GAST-Net state dict and lift_spec an optional
         models.gastnet.GastNetSpec (default: the rf = 27 model in chunks of GAST_CHUNK output frames); the lifting net is a
         wrappers.gastnet.GastNetLifter on this cascade's context, 2 x max_persons x k samples wide (a chunk and its mirror image per
@@ -176,19 +175,19 @@ class Cascade:
         self.topdown = ops.TopDown(self.pose_net, self.k, flip_perm=hrnet.flip_perm(self.k, flip_pairs), shift_heatmap=shift,
                                    post=post, blur_kernel=blur_kernel)
         self.lifter = lifter
-        self.gast = None
+        # lift_model: the one lifter object (lift_many(xs), its net and spec, and what it says of itself: stream_rule, samples_per_chunk)
+        self.gast = None              # the same object, for callers that want GAST-Net's host chain (GastNetLifter.lift)
+        lift_blob = lambda prog: blob_fn("lift", prog)
         if lifter == "GastNet":
             from .models import gastnet as gn
             from .wrappers.gastnet import GastNetLifter
-            self.lift_spec = gn.GastNetSpec(chunk=GAST_CHUNK) if lift_spec is None else lift_spec
-            k_items = -(-(chunk + 2 * self.lift_spec.pad) // self.lift_spec.chunk)
-            self.gast = GastNetLifter(ctx=ctx, numerics=numerics, state_dict=lift_sd, spec=self.lift_spec, flip_augment=True,
-                                      max_batch=2 * max(1, max_persons) * k_items, blob_fn=lambda prog: blob_fn("lift", prog))
-            self.lift_net = self.gast.net
+            lift_spec = gn.GastNetSpec(chunk=GAST_CHUNK) if lift_spec is None else lift_spec
+            k_items = -(-(chunk + 2 * lift_spec.pad) // lift_spec.chunk)
+            self.gast = self.lift_model = GastNetLifter(ctx=ctx, numerics=numerics, state_dict=lift_sd, spec=lift_spec, flip_augment=True,
+                                                        max_batch=2 * max(1, max_persons) * k_items, blob_fn=lift_blob)
         else:
-            self.lift_spec = vp3d.VideoPose3DSpec()
-            lift_prog = vp3d.build_videopose3d_program(self.lift_spec, lift_sd)
-            self.lift_net = Net(ctx, lift_prog, max_batch=max(1, max_persons), blob_dev=blob_fn("lift", lift_prog), numerics=numerics)
+            self.lift_model = VideoPose3DLifter(ctx, lift_sd, max_batch=max(1, max_persons), numerics=numerics, blob_fn=lift_blob)
+        self.lift_net, self.lift_spec = self.lift_model.net, self.lift_model.spec
         # lanes per program (pp_net_set_lane_count; results identical for any count): measured round 6 on the 1080p cascade, see LANES
         env_det, env_pose = os.environ.get("POSEPIPE_DET_LANES"), os.environ.get("POSEPIPE_POSE_LANES")
         det_lanes = int(env_det) if env_det else (LANES["detector"] if det_lanes is None else det_lanes)
@@ -231,13 +230,11 @@ class Cascade:
             for net in (getattr(det, "net_a", None), getattr(det, "net_b", None)):
                 if net is not None:
                     net.close()
-        if getattr(self, "gast", None) is not None:
-            self.gast.close()             # its net is lift_net; the context stays the caller's
-            self.gast, self.lift_net = None, None
-        for name in ("pose_net", "lift_net"):
-            net = getattr(self, name, None)
-            if net is not None:
-                net.close()
+        if getattr(self, "lift_model", None) is not None:
+            self.lift_model.close()       # its net is lift_net; the context stays the caller's
+            self.lift_model = self.gast = self.lift_net = None
+        if getattr(self, "pose_net", None) is not None:
+            self.pose_net.close()
         # the "stream" look-ahead's own context (everything that lived on it is closed above); the caller's ctx stays the caller's
         if self.det_ctx is not self.ctx:
             self.det_ctx.close()
@@ -257,20 +254,12 @@ class Cascade:
             self.tracker = SortReidTracker()
         else:
             self.tracker = Tracker(mode=1, match_iou_thr=0.5, obj_score_thr=self.tracker_score_thr)
-        if self.gast is not None:     # GAST-Net: the stream hands over compacted, converted (n, 17, 2) rows (person_stream.py)
-            self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs,
-                                         lambda x: self.gast.lift_many([x])[0], max_persons=self.max_persons,
-                                         keep_tracks=self.keep_tracks, lift_many_fn=self.gast.lift_many if self.batched_lift else None,
-                                         lifter="GastNet")
-            return
-        # the lifting network takes the 17 COCO joints; wider heads (Halpe-136 / WholeBody-133) start with them
-        self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs,
-                                     lambda kn: lift(self.lift_net, self.lift_spec, kn[:, :17]),
+        # what a stream hands over is its rule's business (person_stream.py): VideoPose3D (n, K, 2) rows with the zero rows in place,
+        # GAST-Net the compacted, converted (n, 17, 2) rows of the valid frames
+        model = self.lift_model
+        self.persons = PersonStreams(self.k, self.lift_spec.pad, self.src, self._topdown_jobs, lambda x: model.lift_many([x])[0],
                                      max_persons=self.max_persons, keep_tracks=self.keep_tracks,
-                                     lift_many_fn=self._lift_many if self.batched_lift else None)
-
-    def _lift_many(self, kns):
-        return lift_many(self.lift_net, self.lift_spec, [kn[:, :17] for kn in kns])
+                                     lift_many_fn=model.lift_many if self.batched_lift else None, lifter=model.stream_rule)
 
     @property
     def n_frames(self):
@@ -280,9 +269,8 @@ class Cascade:
     def flops_per_frame(self):
         """algorithmic conv FLOPs per frame at max_persons persons (detector + 2 x HRNet per person + lifting; GAST-Net: both samples
         of a chunk, the window and its mirror image)"""
-        samples = 2 if self.gast is not None else 1
         return (self.detector.flops_per_frame + 2 * self.max_persons * self.pose_net.prog.flops +
-                samples * self.max_persons * self.lift_net.prog.flops / self.lift_spec.chunk)
+                self.lift_model.samples_per_chunk * self.max_persons * self.lift_net.prog.flops / self.lift_spec.chunk)
 
     # ---- stage 1: detect + associate ------------------------------------------------------------------------
     @staticmethod

@@ -13,10 +13,6 @@
 #include "det_internal.h"
 #include "pp_amax.h"
 
-int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
-int pp_net_max_batch(pp_net* net);
-pp_ctx* pp_net_ctx(pp_net* net);
-
 struct pp_detector {
     pp_ctx* ctx = nullptr;
     pp_net* netA = nullptr;   // image -> FPN levels + RPN maps

@@ -8,7 +8,7 @@
 // merge and camera rotation as two kernels around the program.
 // Both ops are float32 on the vector ALU and memory bound: every input element is read from global memory once, every output written
 // once.  exp is evaluated in double and rounded once (the header's convention).  No atomics: every sum has one fixed order.
-#include "pp_internal.h"
+#include "chunked_lift.h"
 
 #include <algorithm>
 #include <climits>
@@ -209,23 +209,14 @@ int pp_launch_joint_attn(const float* qkv, float* out, int n, int h, int w, int 
 }
 
 // ---- pp_gastnet_lift_many ----------------------------------------------------------------------------------------------------------
-// The chunk loop of wrappers/gastnet.lift_chunks for every track of a call, on the device (the shape of lifting.hip): a work item is
-// one (segment, chunk of T output frames) pair; with flip it takes two batch samples, the window and its mirror image, next to each
-// other.  gast_pack_kernel writes the samples of one batch group from the packed tracks, the program runs, gast_merge_kernel averages
-// each pair, rotates into world space and scatters the item's frames into the packed result.  One upload of tracks and work table,
-// one download, one synchronisation per call.  Every float32 operation of the merge is one rounded product, sum or difference in the
-// order of the host formula (wrappers/gastnet.lift_chunks, camera_to_world): the result is the host's, bit for bit.
-int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
-int pp_net_max_batch(pp_net* net);
-pp_ctx* pp_net_ctx(pp_net* net);
-void pp_net_void_input_amax(pp_net* net, int buf);
-
+// The chunk loop of wrappers/gastnet.lift_chunks for every track of a call, on the device, through the driver VideoPose3D uses
+// (chunked_lift.h: work table, staging, the loop over the batch groups, download, one synchronisation per call): a work item is one
+// (segment, chunk of T output frames) pair; with flip it takes two batch samples, the window and its mirror image, next to each
+// other.  Here are the two kernels around the program and the entry's argument checks: gast_pack_kernel writes the samples of one
+// batch group from the packed tracks, gast_merge_kernel averages each pair, rotates into world space and scatters the item's frames
+// into the packed result.  Every float32 operation of the merge is one rounded product, sum or difference in the order of the host
+// formula (wrappers/gastnet.lift_chunks, camera_to_world): the result is the host's, bit for bit.
 namespace {
-
-// per work item: first row of its segment in the packed arrays, rows of the segment, first output frame of the chunk
-struct GastItem {
-    int32_t base, len, t0;
-};
 
 struct GastQuat {
     float w, x, y, z;
@@ -239,14 +230,14 @@ __device__ __forceinline__ int gast_mirror(int j) {
 
 // in[item * S + s][j][w][0 .. 3] = (x, y, 0, 0) of frame clamp(t0 - pad + w, 0, len - 1) of the item's segment (np.pad 'edge', and the
 // last chunk filled up with its last frame); sample s = 1: joint mirror(j) with x negated.  One thread per float4.
-__global__ __launch_bounds__(256) void gast_pack_kernel(const float2* __restrict__ src, const GastItem* __restrict__ items, int total,
+__global__ __launch_bounds__(256) void gast_pack_kernel(const float2* __restrict__ src, const LiftItem* __restrict__ items, int total,
                                                          int iw, int pad, int S, float4* __restrict__ in) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int w = idx % iw;
     const int j = (idx / iw) % GJ;
     const int smp = idx / (iw * GJ);
-    const GastItem it = items[smp / S];
+    const LiftItem it = items[smp / S];
     const bool mir = (smp % S) != 0;
     int row = it.t0 - pad + w;
     row = row < 0 ? 0 : (row >= it.len ? it.len - 1 : row);
@@ -262,14 +253,14 @@ __device__ __forceinline__ void gast_cross(float qx, float qy, float qz, const f
 }
 
 // dst[base + t0 + r][j] = rotate((y0[j][r] + mirror(y1)[j][r]) / 2) for r < min(T, len - t0).  One thread per (item, joint, frame).
-__global__ __launch_bounds__(256) void gast_merge_kernel(const float* __restrict__ out, const GastItem* __restrict__ items, int total,
+__global__ __launch_bounds__(256) void gast_merge_kernel(const float* __restrict__ out, const LiftItem* __restrict__ items, int total,
                                                           int T, int S, int rotate, GastQuat q, float* __restrict__ dst) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int r = idx % T;
     const int j = (idx / T) % GJ;
     const int ci = idx / (T * GJ);
-    const GastItem it = items[ci];
+    const LiftItem it = items[ci];
     if (r >= it.len - it.t0) return;
     const float* y0 = out + (((size_t)ci * S * GJ + j) * T + r) * 3;
     float v[3] = {y0[0], y0[1], y0[2]};
@@ -290,54 +281,6 @@ __global__ __launch_bounds__(256) void gast_merge_kernel(const float* __restrict
     d[0] = v[0];
     d[1] = v[1];
     d[2] = v[2];
-}
-
-// everything of one call up to, not including, the final synchronisation; `items` must outlive that synchronisation
-int gast_lift_many_enqueue(pp_net* net, pp_ctx* ctx, int in_buf, int out_buf, const float* kpts_norm, const std::vector<GastItem>& items,
-                           size_t rows, int pad, int iw, int T, int S, const float* cam_quat, float* out, int mem) {
-    hipStream_t s = ctx->stream;
-    const int per_group = pp_net_max_batch(net) / S;          // items per batch group
-    const bool host = mem == PP_MEM_HOST;
-    const size_t in_e = rows * GJ * 2, out_e = rows * GJ * 3;
-    int rc = ctx->ensure_scratch(ScratchCursor::align(items.size() * sizeof(GastItem)) +
-                                 (host ? ScratchCursor::align(in_e * sizeof(float)) + ScratchCursor::align(out_e * sizeof(float)) : 0));
-    if (rc != PP_OK) return rc;
-    ScratchCursor cur(ctx);
-    GastItem* d_items = cur.take<GastItem>(items.size());
-    const float* d_src = kpts_norm;
-    float* d_dst = out;
-    if (host) {
-        float* staged = cur.take<float>(in_e);
-        d_dst = cur.take<float>(out_e);
-        PP_HIP_CHECK(hipMemcpyAsync(staged, kpts_norm, in_e * sizeof(float), hipMemcpyHostToDevice, s));
-        d_src = staged;
-    }
-    PP_REQUIRE((reinterpret_cast<uintptr_t>(d_src) & 7) == 0, "pp_gastnet_lift_many: kpts_norm must be 8-byte aligned");
-    PP_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GastItem), hipMemcpyHostToDevice, s));
-    void *in_ptr = nullptr, *out_ptr = nullptr;
-    rc = pp_net_buffer(net, in_buf, &in_ptr, nullptr);
-    if (rc == PP_OK) rc = pp_net_buffer(net, out_buf, &out_ptr, nullptr);
-    if (rc != PP_OK) return rc;
-    PP_REQUIRE(aligned16(in_ptr), "pp_gastnet_lift_many: the program's input buffer must be 16-byte aligned");
-    GastQuat q{1.f, 0.f, 0.f, 0.f};
-    if (cam_quat) q = GastQuat{cam_quat[0], cam_quat[1], cam_quat[2], cam_quat[3]};
-    const int n_items = (int)items.size();
-    for (int c0 = 0; c0 < n_items; c0 += per_group) {
-        const int b = std::min(per_group, n_items - c0);
-        int total = b * S * GJ * iw;
-        hipLaunchKernelGGL(gast_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(d_src),
-                           d_items + c0, total, iw, pad, S, static_cast<float4*>(in_ptr));
-        PP_HIP_CHECK(hipGetLastError());
-        pp_net_void_input_amax(net, in_buf);      // the input was just overwritten here, not by pp_net_forward: the net takes its maxima
-        rc = pp_net_run(net, b * S, 0, -1);
-        if (rc != PP_OK) return rc;
-        total = b * GJ * T;
-        hipLaunchKernelGGL(gast_merge_kernel, dim3((total + 255) / 256), dim3(256), 0, s, static_cast<const float*>(out_ptr), d_items + c0,
-                           total, T, S, cam_quat ? 1 : 0, q, d_dst);
-        PP_HIP_CHECK(hipGetLastError());
-    }
-    if (host) PP_HIP_CHECK(hipMemcpyAsync(out, d_dst, out_e * sizeof(float), hipMemcpyDeviceToHost, s));
-    return PP_OK;
 }
 
 }  // namespace
@@ -365,18 +308,24 @@ extern "C" int pp_gastnet_lift_many(pp_net* net, int in_buf, int out_buf, const 
                ih, iw, ic, oh, ow, oc, pad);
     const int T = ow;
     PP_REQUIRE((size_t)max_b * GJ * iw <= (size_t)INT_MAX, "pp_gastnet_lift_many: batch of %d samples of %d time steps is too large", max_b, iw);
-    std::vector<GastItem> items;                  // one per (segment, chunk), segment after segment
-    int32_t base = 0;
-    for (int i = 0; i < n_seg; ++i) {
-        for (int32_t t0 = 0; t0 < seg_len[i]; t0 += T) items.push_back({base, seg_len[i], t0});
-        base += seg_len[i];
-    }
-    pp_ctx* ctx = pp_net_ctx(net);
+    GastQuat q{1.f, 0.f, 0.f, 0.f};
+    if (cam_quat) q = GastQuat{cam_quat[0], cam_quat[1], cam_quat[2], cam_quat[3]};
+    const int rotate = cam_quat ? 1 : 0;
+    // src: the packed tracks where the kernel reads them (a host array's staged copy).  Both refusals are the same for every group of
+    // a call, so a refused call has launched nothing.
+    auto pack = [=](hipStream_t s, const float* src, const LiftItem* items, int b, void* in) -> int {
+        PP_REQUIRE((reinterpret_cast<uintptr_t>(src) & 7) == 0, "pp_gastnet_lift_many: kpts_norm must be 8-byte aligned");
+        PP_REQUIRE(aligned16(in), "pp_gastnet_lift_many: the program's input buffer must be 16-byte aligned");
+        const int total = b * S * GJ * iw;
+        hipLaunchKernelGGL(gast_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(src), items, total,
+                           iw, pad, S, static_cast<float4*>(in));
+        return PP_OK;
+    };
+    auto merge = [=](hipStream_t s, const float* net_out, const LiftItem* items, int b, float* dst) -> int {
+        const int total = b * GJ * T;
+        hipLaunchKernelGGL(gast_merge_kernel, dim3((total + 255) / 256), dim3(256), 0, s, net_out, items, total, T, S, rotate, q, dst);
+        return PP_OK;
+    };
     PpRange range("pp_gastnet_lift_many");
-    int rc = gast_lift_many_enqueue(net, ctx, in_buf, out_buf, kpts_norm, items, rows, pad, iw, T, S, cam_quat, out, mem);
-    // one synchronisation per call, also after an error: `items` and the caller's host arrays are read by queued copies
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (rc != PP_OK) return rc;
-    PP_HIP_CHECK(e);
-    return PP_OK;
+    return chunked_lift(net, in_buf, out_buf, kpts_norm, seg_len, n_seg, rows, T, S, GJ * 2, GJ * 3, out, mem, pack, merge);
 }

@@ -10,24 +10,15 @@
 //
 // A work item is one (segment, chunk) pair and occupies one batch sample; items of different segments share a
 // batch.  The windows are assembled on the device: lift_gather_kernel writes the program's input buffer from the
-// packed tracks, lift_scatter_kernel copies the valid rows of the output buffer into the packed result.  A call
-// uploads the tracks and a small work table once, queues (gather, program, scatter) per batch group, downloads
-// once and synchronises once.  pp_videopose3d_lift is the one-segment, host-memory case of the same code.
-#include "pp_internal.h"
+// packed tracks, lift_scatter_kernel copies the valid rows of the output buffer into the packed result.  This file
+// holds the two kernels and the entry points' argument checks; the work table, the staging, the (gather, program,
+// scatter) loop over the batch groups, the download and the one synchronisation per call are chunked_lift.h's
+// driver, which GAST-Net shares.  pp_videopose3d_lift is the one-segment, host-memory case of the same code.
+#include "chunked_lift.h"
 
 #include <climits>
 
-int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
-int pp_net_max_batch(pp_net* net);
-pp_ctx* pp_net_ctx(pp_net* net);
-void pp_net_void_input_amax(pp_net* net, int buf);
-
 namespace {
-
-// per work item: first row of its segment in the packed arrays, rows of the segment, first output frame of the chunk
-struct LiftItem {
-    int32_t base, len, t0;
-};
 
 // in[ci][j][c] = c < in_features ? src[base + clamp(t0 - pad + j, 0, len - 1)][c] : 0, for the items of one batch group.
 // V = float2 when both channel counts are even (34 -> 36 floats = 17 -> 18 float2), else float; the counts are in units of V.
@@ -61,57 +52,6 @@ __global__ void lift_scatter_kernel(const float* __restrict__ out, const LiftIte
 
 bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
-// everything of one call up to, not including, the final synchronisation; `items` must outlive that synchronisation
-int lift_many_enqueue(pp_net* net, pp_ctx* ctx, int in_buf, int out_buf, const float* kpts2d_norm, const std::vector<LiftItem>& items,
-                      size_t rows, int in_features, int pad, int iw, int ic, int T, int oc, float* out, int mem) {
-    hipStream_t s = ctx->stream;
-    const int max_b = pp_net_max_batch(net);
-    const bool host = mem == PP_MEM_HOST;
-    const size_t in_e = rows * in_features, out_e = rows * oc;
-    int rc = ctx->ensure_scratch(ScratchCursor::align(items.size() * sizeof(LiftItem)) +
-                                 (host ? ScratchCursor::align(in_e * sizeof(float)) + ScratchCursor::align(out_e * sizeof(float)) : 0));
-    if (rc != PP_OK) return rc;
-    ScratchCursor cur(ctx);
-    LiftItem* d_items = cur.take<LiftItem>(items.size());
-    const float* d_src = kpts2d_norm;
-    float* d_dst = out;
-    if (host) {
-        float* staged = cur.take<float>(in_e);
-        d_dst = cur.take<float>(out_e);
-        PP_HIP_CHECK(hipMemcpyAsync(staged, kpts2d_norm, in_e * sizeof(float), hipMemcpyHostToDevice, s));
-        d_src = staged;
-    }
-    PP_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(LiftItem), hipMemcpyHostToDevice, s));
-    void *in_ptr = nullptr, *out_ptr = nullptr;
-    rc = pp_net_buffer(net, in_buf, &in_ptr, nullptr);
-    if (rc == PP_OK) rc = pp_net_buffer(net, out_buf, &out_ptr, nullptr);
-    if (rc != PP_OK) return rc;
-    const bool vec2 = in_features % 2 == 0 && ic % 2 == 0 && aligned8(d_src) && aligned8(in_ptr);
-    const int n_items = (int)items.size();
-    for (int c0 = 0; c0 < n_items; c0 += max_b) {
-        const int b = std::min(max_b, n_items - c0);
-        if (vec2) {
-            const int total = b * iw * (ic / 2);
-            hipLaunchKernelGGL(lift_gather_kernel<float2>, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(d_src),
-                               d_items + c0, total, iw, ic / 2, in_features / 2, pad, static_cast<float2*>(in_ptr));
-        } else {
-            const int total = b * iw * ic;
-            hipLaunchKernelGGL(lift_gather_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, s, d_src, d_items + c0, total, iw, ic,
-                               in_features, pad, static_cast<float*>(in_ptr));
-        }
-        PP_HIP_CHECK(hipGetLastError());
-        pp_net_void_input_amax(net, in_buf);      // the input was just overwritten here, not by pp_net_forward
-        rc = pp_net_run(net, b, 0, -1);
-        if (rc != PP_OK) return rc;
-        const int total = b * T * oc;
-        hipLaunchKernelGGL(lift_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, s, static_cast<const float*>(out_ptr), d_items + c0,
-                           total, T, oc, d_dst);
-        PP_HIP_CHECK(hipGetLastError());
-    }
-    if (host) PP_HIP_CHECK(hipMemcpyAsync(out, d_dst, out_e * sizeof(float), hipMemcpyDeviceToHost, s));
-    return PP_OK;
-}
-
 // `who`: the entry point the caller used, for the messages
 int lift_many(const char* who, pp_net* net, int in_buf, int out_buf, const float* kpts2d_norm, const int32_t* seg_frames, int n_segs,
               int in_features, int out_features, int pad, float* out, int mem) {
@@ -132,20 +72,25 @@ int lift_many(const char* who, pp_net* net, int in_buf, int out_buf, const float
                "%s: program shape (in %dx%dx%d, out %dx%dx%d) does not match pad=%d / features %d->%d",
                who, ih, iw, ic, oh, ow, oc, pad, in_features, out_features);
     const int T = ow;
-    std::vector<LiftItem> items;                  // one per (segment, chunk), segment after segment
-    int32_t base = 0;
-    for (int i = 0; i < n_segs; ++i) {
-        for (int32_t t0 = 0; t0 < seg_frames[i]; t0 += T) items.push_back({base, seg_frames[i], t0});
-        base += seg_frames[i];
-    }
-    pp_ctx* ctx = pp_net_ctx(net);
+    auto gather = [=](hipStream_t s, const float* src, const LiftItem* items, int b, void* in) -> int {
+        if (in_features % 2 == 0 && ic % 2 == 0 && aligned8(src) && aligned8(in)) {
+            const int total = b * iw * (ic / 2);
+            hipLaunchKernelGGL(lift_gather_kernel<float2>, dim3((total + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2*>(src),
+                               items, total, iw, ic / 2, in_features / 2, pad, static_cast<float2*>(in));
+        } else {
+            const int total = b * iw * ic;
+            hipLaunchKernelGGL(lift_gather_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, s, src, items, total, iw, ic,
+                               in_features, pad, static_cast<float*>(in));
+        }
+        return PP_OK;
+    };
+    auto scatter = [=](hipStream_t s, const float* net_out, const LiftItem* items, int b, float* dst) -> int {
+        const int total = b * T * oc;
+        hipLaunchKernelGGL(lift_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, s, net_out, items, total, T, oc, dst);
+        return PP_OK;
+    };
     PpRange range("pp_videopose3d_lift_many");
-    int rc = lift_many_enqueue(net, ctx, in_buf, out_buf, kpts2d_norm, items, rows, in_features, pad, iw, ic, T, oc, out, mem);
-    // one synchronisation per call, also after an error: `items` and the caller's host arrays are read by queued copies
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (rc != PP_OK) return rc;
-    PP_HIP_CHECK(e);
-    return PP_OK;
+    return chunked_lift(net, in_buf, out_buf, kpts2d_norm, seg_frames, n_segs, rows, T, 1, in_features, oc, out, mem, gather, scatter);
 }
 
 }  // namespace

@@ -13,12 +13,6 @@
 #include <algorithm>
 #include <climits>
 
-int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
-int pp_net_max_batch(pp_net* net);
-pp_ctx* pp_net_ctx(pp_net* net);
-void pp_net_void_input_amax(pp_net* net, int buf);
-const float* pp_net_weights(pp_net* net, size_t* n_weights);
-
 namespace {
 
 __device__ __forceinline__ float pf_gelu(float x) {
@@ -417,12 +411,7 @@ extern "C" int pp_poseformer_spatial(pp_ctx* ctx, const float* params, const flo
     }
     int rc = launch_spatial(d_k, params, features, n_frames, ctx->stream);
     // the staged copy reads the caller's host array: complete on return
-    if (kpts_mem == PP_MEM_HOST) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (rc != PP_OK) return rc;
-        PP_HIP_CHECK(e);
-    }
-    return rc;
+    return kpts_mem == PP_MEM_HOST ? pp_sync_after(ctx->stream, rc) : rc;
 }
 
 namespace {
@@ -498,9 +487,8 @@ extern "C" int pp_poseformer_lift(pp_net* net, int in_buf, int out_buf, long lon
     StageTimer tm(stage_ms != nullptr);
     int rc = poseformer_enqueue(net, ctx, in_buf, out_buf, w, spatial_off, pos_off, head_off, kpts2d_norm, n_frames, ic, out, mem, tm);
     // one synchronisation per call, also after an error: the caller's host arrays are read by queued copies
-    hipError_t e = hipStreamSynchronize(ctx->stream);
+    rc = pp_sync_after(ctx->stream, rc);
     if (rc != PP_OK) return rc;
-    PP_HIP_CHECK(e);
     if (stage_ms) {
         for (int k = 0; k < 4; ++k) stage_ms[k] = 0.f;
         tm.collect(stage_ms);

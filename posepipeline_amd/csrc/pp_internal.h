@@ -74,6 +74,24 @@ struct ScratchCursor {
     }
 };
 
+// The tail of an entry whose queued copies read host arrays that must outlive them: one synchronisation, also after an error.  `rc`,
+// the status of what was enqueued, goes first.
+inline int pp_sync_after(hipStream_t stream, int rc) {
+    hipError_t e = hipStreamSynchronize(stream);
+    if (rc != PP_OK) return rc;
+    PP_HIP_CHECK(e);
+    return PP_OK;
+}
+
+// ---- what the stages built around a layer program read of it (net.hip) ----------------------------------------------------------
+int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
+int pp_net_max_batch(pp_net* net);
+pp_ctx* pp_net_ctx(pp_net* net);
+// the resident weight blob (device pointer) and its length in floats
+const float* pp_net_weights(pp_net* net, size_t* n_weights);
+// the caller's own kernel has just overwritten `buf`: a pending promise of its maxima (pp_net_input_amax) is void
+void pp_net_void_input_amax(pp_net* net, int buf);
+
 // ---- roctx ranges around the stages (rocprofv3 --marker-trace shows them on the host timeline, each enclosing the
 // launches of one stage; the per-stage DEVICE times are the HIP-event figures of pp_detector_timing / pp_topdown_timing).  The
 // marker library is looked up at run time (librocprofiler-sdk-roctx.so, else libroctx64.so): absent = no-ops, no link dependency.

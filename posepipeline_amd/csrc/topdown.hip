@@ -27,11 +27,6 @@ struct pp_topdown {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // start | after pre | after net | after decode
 };
 
-// implemented in api_core.hip
-int pp_net_dims(pp_net* net, int buf, int* h, int* w, int* c);
-int pp_net_max_batch(pp_net* net);
-pp_ctx* pp_net_ctx(pp_net* net);
-
 extern "C" void pp_topdown_destroy(pp_topdown* t);
 
 extern "C" {

@@ -28,6 +28,12 @@ The compute stages are callables, so this module needs no GPU (tests/test_person
     lift_many_fn(kns) optional: kns = list of such contexts -> list of (n_i, J, 3), element i equal to lift_fn(kns[i]); when given,
                       advance() makes ONE call with the contexts of every stream instead of one lift_fn call per stream
 
+Structure: `_PersonStream` holds what does not depend on the lifter (the box decisions of one track id); a lifter's temporal rule is
+a subclass that owns its rows (`_FrameWindows`: VideoPose3D, `_ValidWindows`: GAST-Net; `push` takes the new 2D rows, `emit` says
+which frames can be emitted now, what has to be lifted for them and where the lifted rows go).  `PersonStreams.advance` is one path
+for both: decide boxes, run the 2D stage, hand every stream its rows, collect the contexts the streams hand back, lift them in one
+call (or one after the other, in ascending track-id order), place the results.
+
 `PersonStreams(lifter="GastNet")` streams the reference's DEFAULT lifting method instead (LiftingMethodLookup row 0,
 wrappers/gastnet.process_gastnet), whose temporal rule is another one: GAST-Net drops the invalid frames of a track and lifts the
 COMPACTED sequence of the valid ones, where VideoPose3D keeps zero rows in place.
@@ -62,25 +68,28 @@ FILL_LIMIT = 2          # PersonBbox.make: fillna(method="bfill"/"ffill", limit=
 
 
 class _PersonStream:
-    """Streaming PersonBbox(keep_tracks=[tid]) -> TopDownPerson -> LiftingPerson state of one track id."""
+    """Streaming PersonBbox(keep_tracks=[tid]) -> TopDownPerson -> LiftingPerson state of one track id: the box decisions, which do
+    not depend on the lifter.  A lifter's temporal rule is a subclass with its own state and two methods:
 
-    def __init__(self, tid: int, born: int, num_joints: int):
+        push(rows, absent)            the 2D rows (K,3) decided last, consecutive frames (zero rows where the box stayed NaN; absent:
+                                      there is one among them)
+        emit(bound, closed, n_total)  bound: first frame that cannot be emitted yet; closed: no further row will come; n_total: the
+                                      clip's length once it is known, else None.  -> None, or (m, context, place, more) and next3d moved
+                                      on by m > 0: frames [next3d - m, next3d) are emitted now; context: what to lift for them, or None
+                                      when nothing is; place(lifted context, or None) -> their (m, J, 3) block; more: {name: (m,) per-
+                                      frame values} for the names in `extra`.  Also forgets the rows no later window will read."""
+
+    extra = ()                                   # names of what the rule emits per frame beside keypoints_3d
+
+    def __init__(self, tid: int, born: int, num_joints: int, pad: int, src_hw):
         self.tid = tid
         self.first = max(0, born - FILL_LIMIT)   # first frame with a (back-filled) box
         self.raw: dict = {}                      # frame -> tlwh of frames whose neighbours' fills are still open
         self.last_raw = born                     # last frame with a raw (un-filled) box
         self.next_dec = self.first               # next frame whose box has not been decided
-        self.k2_base = self.first                # frame index of k2[0]
-        self.k2: list = []                       # decided 2D rows (K,3) float32, zeros where the box stayed NaN
         self.next3d = self.first                 # next frame whose 3D has not been emitted
-        self.any_absent = self.first > 0         # reference: a zero row makes the clip's key-point array float64
         self.live = True
-        self.k = num_joints
-        # lifter="GastNet": the compacted sequence of valid frames
-        self.g_flags: list = []                  # validity of the decided frames from next3d on (not yet emitted)
-        self.g_rows: list = []                   # normalised (17,2) float32 rows of the valid frames a window can still read
-        self.g_base = 0                          # index, in the valid sequence, of g_rows[0]
-        self.g_next = 0                          # index, in the valid sequence, of the next valid frame to lift
+        self.k, self.pad, self.src = num_joints, pad, src_hw
 
     def decide(self, n_frames: int, final: bool):
         """Box decisions for frames [next_dec, n_frames) in order, as far as they can be made.  final: nothing will
@@ -107,6 +116,20 @@ class _PersonStream:
             raw.pop(t - FILL_LIMIT, None)            # nothing looks further back than 2 frames
             yield t, box
 
+
+class _FrameWindows(_PersonStream):
+    """VideoPose3D's rule: zero rows stay in place, the window of frame t is the frames [t - pad, t + pad] of the clip."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.k2_base = self.first                # frame index of k2[0]
+        self.k2: list = []                       # decided 2D rows (K,3) float32, zeros where the box stayed NaN
+        self.any_absent = self.first > 0         # reference: a zero row makes the clip's key-point array float64
+
+    def push(self, rows, absent: bool):
+        self.any_absent = self.any_absent or absent
+        self.k2.extend(rows)
+
     def row(self, t: int, n_total):
         """2D row of frame t for the lifting context (n_total: clip length when known, else None)."""
         if n_total is not None and t >= n_total:
@@ -118,6 +141,87 @@ class _PersonStream:
             return None                              # before the first box / after the track ended: a zero row
         return self.k2[i]
 
+    def emit(self, bound: int, closed: bool, n_total):
+        pad, lo = self.pad, self.next3d
+        hi = bound if closed else bound - pad        # frame t waits for the key points of frame t + pad
+        got = None
+        if hi > lo:
+            # normalised 2D context [lo - pad, hi + pad): what lifting frames [lo, hi) reads
+            zero = np.zeros((self.k, 3), np.float32)
+            rows = [self.row(t, n_total) for t in range(lo - pad, hi + pad)]
+            arr = np.stack([zero if r is None else r for r in rows])[:, :, :2]
+            arr = arr.astype(np.float64) if self.any_absent else arr          # the reference's dtype-dependent normalisation
+            got = (hi - lo, normalize_screen_coordinates(arr, self.src[1], self.src[0]), lambda out: out[pad:pad + hi - lo], {})
+            self.next3d = hi
+        drop = self.next3d - pad - self.k2_base       # rows no window will read again
+        if drop > 0:
+            del self.k2[:drop]
+            self.k2_base += drop
+        return got
+
+
+class _ValidWindows(_PersonStream):
+    """GAST-Net's rule: the invalid frames are dropped, the window of the i-th VALID frame is valid frames [i - pad, i + pad]."""
+
+    extra = ("keypoints_valid",)
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.flags: list = []                    # validity of the decided frames from next3d on (not yet emitted)
+        self.rows: list = []                     # normalised (17,2) float32 rows of the valid frames a window can still read
+        self.base = 0                            # index, in the valid sequence, of rows[0]
+        self.next_valid = 0                      # index, in the valid sequence, of the next valid frame to lift
+
+    def push(self, rows, absent: bool):
+        """the GAST-Net host chain on the new rows, frame by frame: validity flags and the valid rows, normalised"""
+        if not rows:
+            return
+        from .wrappers import gastnet as gw
+        rows = np.stack(rows)
+        kpts, scores = gw.h36m_rows(rows[:, :gw.NUM_JOINTS, :2], rows[:, :gw.NUM_JOINTS, 2])
+        valid = kpts.reshape(-1, 2 * gw.NUM_JOINTS).sum(axis=1) != 0
+        kpts = gw.revise_kpts(kpts, scores, np.flatnonzero(valid))
+        x = gw.normalize_screen_coordinates(kpts[valid], w=int(self.src[1]), h=int(self.src[0])).astype(np.float32)
+        self.flags.extend(bool(v) for v in valid)
+        self.rows.extend(x)
+
+    def emit(self, bound: int, closed: bool, n_total):
+        pad = self.pad
+        n_valid = self.base + len(self.rows)
+        n_avail = min(len(self.flags), bound - self.next3d)
+        a = b = self.next_valid
+        m = 0
+        while m < n_avail:
+            if self.flags[m]:
+                if not closed and b + pad >= n_valid:
+                    break                            # this valid frame's window is not complete: it, and what follows, waits
+                b += 1
+            m += 1
+        if m == 0:
+            return None
+        mask = np.array(self.flags[:m], bool)
+        ctx_rows, lo = None, a
+        if b > a:                                    # the context [a - pad, b + pad) cut to the valid sequence known so far
+            lo, hi = max(0, a - pad), min(n_valid, b + pad)
+            ctx_rows = np.stack(self.rows[lo - self.base:hi - self.base])
+        del self.flags[:m]
+        self.next3d += m
+        self.next_valid = b
+        drop = b - pad - self.base                   # valid rows no window will read again
+        if drop > 0:
+            del self.rows[:drop]
+            self.base += drop
+
+        def place(out):
+            out3 = np.zeros((m, 17, 3), np.float32)      # zero rows at the invalid frames
+            if b > a:
+                out3[mask] = np.asarray(out)[a - lo:b - lo]
+            return out3
+        return m, ctx_rows, place, {"keypoints_valid": mask}
+
+
+_RULES = {"VideoPose3D": _FrameWindows, "GastNet": _ValidWindows}       # PersonStreams(lifter=...)
+
 
 class PersonStreams:
     """max_persons: tracks followed at the same time (new ids are adopted, in row order, while fewer are live; an id that
@@ -125,11 +229,11 @@ class PersonStreams:
 
     def __init__(self, num_joints: int, pad: int, src_hw, topdown_fn, lift_fn, max_persons: int = 1, keep_tracks=None,
                  lift_many_fn=None, lifter: str = "VideoPose3D"):
-        if lifter not in ("VideoPose3D", "GastNet"):
+        if lifter not in _RULES:
             raise ValueError(f"PersonStreams: lifter = {lifter!r}, expected 'VideoPose3D' or 'GastNet'")
         if lifter == "GastNet" and int(num_joints) < 17:
             raise ValueError(f"PersonStreams: the GAST-Net rule converts the 17 COCO joints; the 2D stage has {num_joints}")
-        self.lifter = lifter
+        self.lifter, self._rule = lifter, _RULES[lifter]
         self.k, self.pad, self.src = int(num_joints), int(pad), tuple(src_hw)
         self.topdown_fn, self.lift_fn, self.lift_many_fn = topdown_fn, lift_fn, lift_many_fn
         self.max_persons = max_persons
@@ -172,7 +276,7 @@ class PersonStreams:
                     if not follow:
                         self.ignored.add(tid)
                         continue
-                    st = self.streams[tid] = _PersonStream(tid, t, self.k)
+                    st = self.streams[tid] = self._rule(tid, t, self.k, self.pad, self.src)
                 if count[tid] == 1:
                     # tlhw as the wrappers store it: [x1, y1, x2 - x1, y2 - y1] on mmtrack's float32 row (wrappers/mmtrack.py:55),
                     # or the tracker's own to_tlwh() when the row carries it as a 7th element (deep_sort_yolov4/parser.py:80)
@@ -180,70 +284,11 @@ class PersonStreams:
                     st.last_raw = t
             self.n_frames += 1
 
-    def _lift_context(self, st: _PersonStream, lo: int, hi: int, n_total):
-        """normalised 2D context [lo - pad, hi + pad) of one stream: what lifting frames [lo, hi) reads"""
-        pad = self.pad
-        zero = np.zeros((self.k, 3), np.float32)
-        rows = [st.row(t, n_total) for t in range(lo - pad, hi + pad)]
-        arr = np.stack([zero if r is None else r for r in rows])[:, :, :2]
-        arr = arr.astype(np.float64) if st.any_absent else arr          # the reference's dtype-dependent normalisation
-        return normalize_screen_coordinates(arr, self.src[1], self.src[0])
-
-    def _lift_range(self, st: _PersonStream, lo: int, hi: int, n_total):
-        """3D of frames [lo, hi) of one stream from the context [lo - pad, hi + pad)"""
-        pad = self.pad
-        out = self.lift_fn(self._lift_context(st, lo, hi, n_total))
-        return out[pad:pad + hi - lo]
-
-    def _gast_convert(self, st: _PersonStream, n_new: int):
-        """the GAST-Net host chain on the n_new rows decided last, frame by frame: validity flags and the valid rows, normalised"""
-        from .wrappers import gastnet as gw
-        rows = np.stack(st.k2[len(st.k2) - n_new:])
-        kpts, scores = gw.h36m_rows(rows[:, :gw.NUM_JOINTS, :2], rows[:, :gw.NUM_JOINTS, 2])
-        valid = kpts.reshape(-1, 2 * gw.NUM_JOINTS).sum(axis=1) != 0
-        kpts = gw.revise_kpts(kpts, scores, np.flatnonzero(valid))
-        x = gw.normalize_screen_coordinates(kpts[valid], w=int(self.src[1]), h=int(self.src[0])).astype(np.float32)
-        st.g_flags.extend(bool(v) for v in valid)
-        st.g_rows.extend(x)
-
-    def _gast_range(self, st: _PersonStream, bound: int, closed: bool):
-        """What stream `st` can emit now, frames [next3d, next3d + m) with m > 0, or None.  bound: first frame that cannot be emitted
-        yet; closed: no further valid frame will come.  -> (m, validity of the m frames, rows to keep = (offset, count) in the lifted
-        context, context (n, 17, 2) or None when no frame of the range is valid); advances the stream's state."""
-        pad = self.pad
-        n_valid = st.g_base + len(st.g_rows)
-        n_avail = min(len(st.g_flags), bound - st.next3d)
-        a = b = st.g_next
-        m = 0
-        while m < n_avail:
-            if st.g_flags[m]:
-                if not closed and b + pad >= n_valid:
-                    break                            # this valid frame's window is not complete: it, and what follows, waits
-                b += 1
-            m += 1
-        if m == 0:
-            return None
-        mask = np.array(st.g_flags[:m], bool)
-        ctx_rows, lo = None, a
-        if b > a:
-            lo, hi = max(0, a - pad), min(n_valid, b + pad)
-            ctx_rows = np.stack(st.g_rows[lo - st.g_base:hi - st.g_base])
-        del st.g_flags[:m]
-        st.next3d += m
-        st.g_next = b
-        drop = b - pad - st.g_base                   # valid rows no window will read again
-        if drop > 0:
-            del st.g_rows[:drop]
-            st.g_base += drop
-        return m, mask, (a - lo, b - a), ctx_rows
-
     def advance(self, final: bool = False):
         """Decide boxes, run 2D, emit 3D for everything that has become computable.  final: end of clip.
         Returns dict(keypoints / keypoints_frames = {track_id: (n,K,3) / (n,) frame numbers} decided in this call,
                      keypoints_3d / keypoints_3d_frames = {track_id: (m,J,3) / (m,)} emitted in this call;
                      lifter="GastNet": also keypoints_valid / keypoints_valid_frames = {track_id: (m,) bool / (m,)})."""
-        gast = self.lifter == "GastNet"
-        kpv, gast_jobs = {}, []       # GastNet: (track_id, frames, validity, (offset, count), context) of every range emitted
         n1 = self.n_frames
         jobs, decided = [], {}
         for tid in sorted(self.streams):
@@ -255,83 +300,48 @@ class PersonStreams:
         rows2d = self.topdown_fn(jobs) if jobs else []
         k2 = {(j[0], j[1]): r for j, r in zip(jobs, rows2d)}
         kp, kp_frames, kp3, kp3_frames = {}, {}, {}, {}
-        pad = self.pad
+        more = {name: {} for name in self._rule.extra}
         zero = np.zeros((self.k, 3), np.float32)
-        batched = []                  # lift_many_fn: (track_id, frames lifted, context) of every range that became computable
+        emitted = []                  # (track_id, context or None, place) of every range emitted, in ascending track-id order
         for tid in sorted(self.streams):
             st = self.streams[tid]
             ts = decided.get(tid, [])
-            for t in ts:
-                row = k2.get((tid, t))
-                if row is None:
-                    st.any_absent = True
-                    row = zero
-                st.k2.append(row)
+            new = [k2.get((tid, t)) for t in ts]
+            rows = [zero if r is None else r for r in new]
+            st.push(rows, any(r is None for r in new))
             # a dropped track owes nothing past its last (forward-filled) box: the rows after it are zero rows for good
             cap = None if st.live else st.last_raw + FILL_LIMIT + 1
             te = [t for t in ts if cap is None or t < cap]
             if te:
-                kp[tid] = np.stack(st.k2[te[0] - st.k2_base: te[-1] + 1 - st.k2_base])
+                kp[tid] = np.stack(rows[:len(te)])
                 kp_frames[tid] = np.array(te, np.int64)
             # ... and is finalised once its last decided row is one of those zero rows
             ended = (not st.live) and st.next_dec > cap
-            if gast:
-                if ts:
-                    self._gast_convert(st, len(ts))
-                got = self._gast_range(st, st.next_dec if cap is None else min(st.next_dec, cap), final or ended)
-                if got is not None:
-                    kp3_frames[tid] = np.arange(st.next3d - got[0], st.next3d, dtype=np.int64)
-                    kpv[tid] = got[1]
-                    gast_jobs.append((tid,) + got)
-                if final or ended:
-                    del self.streams[tid]
-                    self.finished.add(tid)
-                else:
-                    del st.k2[:]                      # the compacted rows are kept instead (g_rows)
-                    st.k2_base = st.next_dec
-                continue
-            if final:
-                hi, n_total = st.next_dec if cap is None else min(st.next_dec, cap), n1
-            elif ended:
-                hi, n_total = cap, None
-            else:
-                hi, n_total = st.next_dec - pad, None
-            if hi > st.next3d:
-                if self.lift_many_fn is None:
-                    kp3[tid] = self._lift_range(st, st.next3d, hi, n_total)
-                else:                 # the context is built here, from the rows the stream holds now; lifted below, all at once
-                    batched.append((tid, hi - st.next3d, self._lift_context(st, st.next3d, hi, n_total)))
-                kp3_frames[tid] = np.arange(st.next3d, hi, dtype=np.int64)
-                st.next3d = hi
+            got = st.emit(st.next_dec if cap is None else min(st.next_dec, cap), final or ended, n1 if final else None)
+            if got is not None:
+                m, context, place, vals = got
+                kp3_frames[tid] = np.arange(st.next3d - m, st.next3d, dtype=np.int64)
+                for name in more:
+                    more[name][tid] = vals[name]
+                emitted.append((tid, context, place))
             if final or ended:
                 del self.streams[tid]
                 self.finished.add(tid)
-            else:
-                drop = st.next3d - pad - st.k2_base       # rows no window will read again
-                if drop > 0:
-                    del st.k2[:drop]
-                    st.k2_base += drop
-        if batched:
-            lifted = self.lift_many_fn([kn for _, _, kn in batched])
-            assert len(lifted) == len(batched), (len(lifted), len(batched))
-            for (tid, n, _), out in zip(batched, lifted):
-                kp3[tid] = out[pad:pad + n]
-        if gast:
-            todo = [j for j in gast_jobs if j[4] is not None]
-            if todo and self.lift_many_fn is not None:
-                lifted = self.lift_many_fn([j[4] for j in todo])
-                assert len(lifted) == len(todo), (len(lifted), len(todo))
-            else:
-                lifted = [self.lift_fn(j[4]) for j in todo]
-            lifted = {j[0]: out for j, out in zip(todo, lifted)}
-            for tid, m, mask, (off, cnt), _ in gast_jobs:
-                out3 = np.zeros((m, 17, 3), np.float32)
-                if cnt:
-                    out3[mask] = np.asarray(lifted[tid])[off:off + cnt]
-                kp3[tid] = out3
-            return dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames,
-                        keypoints_valid=kpv, keypoints_valid_frames={tid: f.copy() for tid, f in kp3_frames.items()})
-        return dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames)
+        # the contexts are built above, from the rows the streams held then; lifted here, all at once
+        contexts = [c for _, c, _ in emitted if c is not None]
+        if contexts and self.lift_many_fn is not None:
+            lifted = self.lift_many_fn(contexts)
+            assert len(lifted) == len(contexts), (len(lifted), len(contexts))
+        else:
+            lifted = [self.lift_fn(c) for c in contexts]
+        lifted = iter(lifted)
+        for tid, context, place in emitted:
+            kp3[tid] = place(None if context is None else next(lifted))
+        out = dict(keypoints=kp, keypoints_frames=kp_frames, keypoints_3d=kp3, keypoints_3d_frames=kp3_frames)
+        for name, vals in more.items():
+            out[name] = vals
+            out[name + "_frames"] = {tid: kp3_frames[tid].copy() for tid in vals}
+        return out
 
 
 def collect(outs, what="keypoints_3d"):

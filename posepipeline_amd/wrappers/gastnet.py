@@ -172,10 +172,13 @@ class GastNetLifter:
     numerics: as Net's (None: the process default at this moment).  blob_fn(program) -> Net's blob_dev (a weight blob that is already
     on the device) or None."""
 
+    stream_rule = "GastNet"           # person_stream.PersonStreams(lifter=): the valid frames compacted, windows over those
+
     def __init__(self, device=0, numerics=None, ctx=None, state_dict=None, spec=gn.GastNetSpec(), flip_augment=True, max_batch=2,
                  blob_fn=None):
         self.spec = spec
         self.flip_augment = bool(flip_augment)
+        self.samples_per_chunk = 2 if self.flip_augment else 1      # the window and its mirror image
         if max_batch < (2 if self.flip_augment else 1):
             raise ValueError(f"GastNetLifter: max_batch = {max_batch}; flip augmentation needs two samples per chunk")
         sd = load_state_dict(spec) if state_dict is None else weights.strip_key_prefix(state_dict, "module.")

@@ -6,7 +6,8 @@ edge-replicated 243-frame window per frame (ChunkedGenerator, :66-75) and runs
 TemporalModelOptimized1f on the CPU in batches of `batch_size`; here the whole clip goes through the
 dilated program on the GPU (pp_videopose3d_lift), which evaluates the same sums.  `batch_size` and
 `transform_coco` are accepted and, like `transform_coco` in the reference, have no effect on the result.
-`lift_many` lifts several tracks in one device-side call (pp_videopose3d_lift_many); the cascade uses it.
+`lift_many` lifts several tracks in one device-side call (pp_videopose3d_lift_many); the cascade uses it, through a
+`VideoPose3DLifter` (the resident model as an object, GastNetLifter's counterpart).
 """
 from __future__ import annotations
 
@@ -81,6 +82,31 @@ def lift_many(net, spec, kns) -> list:
                "pp_videopose3d_lift_many")
     ends = np.cumsum(seg)
     return [out[e - n:e].reshape(n, spec.num_joints_out, 3) for e, n in zip(ends, seg)]
+
+
+class VideoPose3DLifter:
+    """The resident model as the streamed cascade holds a lifter (the surface of wrappers.gastnet.GastNetLifter): the dilated program
+    on the caller's context, `max_batch` chunks wide.  The network takes the 17 COCO joints; wider heads (Halpe-136 / WholeBody-133)
+    start with them.  blob_fn(program) -> Net's blob_dev (a weight blob that is already on the device) or None."""
+
+    stream_rule = "VideoPose3D"       # person_stream.PersonStreams(lifter=): zero rows stay in place, windows over frames
+    samples_per_chunk = 1             # batch samples the program evaluates per chunk of output frames
+
+    def __init__(self, ctx, state_dict, max_batch=1, numerics=None, blob_fn=None):
+        self.spec = vp3d.VideoPose3DSpec()
+        prog = vp3d.build_videopose3d_program(self.spec, state_dict)
+        self.net = Net(ctx, prog, max_batch=int(max_batch), numerics=numerics, blob_dev=None if blob_fn is None else blob_fn(prog))
+
+    def lift(self, kn) -> np.ndarray:
+        return lift(self.net, self.spec, kn[:, :17])
+
+    def lift_many(self, kns) -> list:
+        return lift_many(self.net, self.spec, [kn[:, :17] for kn in kns])
+
+    def close(self):
+        if self.net is not None:
+            self.net.close()
+            self.net = None
 
 
 def process_videopose3d(key, batch_size=32, transform_coco=False):

@@ -150,6 +150,33 @@ def test_refusals_name_the_cause(ctx, sd_small):
         one.close()
 
 
+def test_a_4_byte_aligned_device_source_is_refused(ctx, sd_small):
+    """gast_pack_kernel reads the source as float2: a device source 4 bytes into its allocation is refused, nothing is written"""
+    segs = _segments((4, 3))
+    lf = W.GastNetLifter(numerics="exact", ctx=ctx, state_dict=sd_small, spec=SMALL, max_batch=2)
+    packed = np.ascontiguousarray(np.concatenate(segs))
+    seg = np.array([len(s) for s in segs], np.int32)
+    filled = np.full((len(packed), 17, 3), SENTINEL, F32)
+    d_in, d_out = ctx.malloc(packed.nbytes + 8), ctx.malloc(filled.nbytes)
+    try:
+        assert d_in % 8 == 0
+        ctx.h2d(d_in + 4, packed)
+        ctx.h2d(d_out, filled)
+        named = lf.net.prog.named
+        rc = ctx.lib.pp_gastnet_lift_many(lf.net.handle, named["input"], named["output"], L.ptr(d_in + 4), L.ptr(seg), len(seg), SMALL.pad,
+                                          1, L.ptr(W.CAMERA_QUATERNION), L.ptr(d_out), L.PP_MEM_DEVICE)
+        err = L.last_error()
+        ctx.synchronize()
+        got = np.zeros_like(filled)
+        ctx.d2h(got, d_out)
+    finally:
+        ctx.free(d_in)
+        ctx.free(d_out)
+        lf.close()
+    assert rc == -1 and "pp_gastnet_lift_many" in err and "8-byte aligned" in err, (rc, err)
+    assert (got == SENTINEL).all()
+
+
 # ---- 4. the table path -------------------------------------------------------------------------------------------------------------
 def test_process_gastnet_equals_the_host_chain(tmp_path, monkeypatch):
     """process_gastnet goes through lift_many([x]); what it stores is what it stored before: zeros + camera_to_world(lift(x))"""

@@ -129,6 +129,35 @@ def test_lift_many_on_device_memory(ctx):
     net.close()
 
 
+def test_lift_many_scalar_gather_on_a_4_byte_aligned_source(ctx):
+    """lift_gather_kernel<float> runs only when a pointer is not 8-byte aligned (2 J features are always even): a device source 4
+    bytes into its allocation must give the bytes of the aligned call (float2 gather)"""
+    spec = vp3d.VideoPose3DSpec(channels=CHANNELS, chunk=32)
+    net = Net(ctx, vp3d.build_videopose3d_program(spec, _state_dict()), max_batch=2)
+    segs = _segments([1, 5, 33], seed=9)
+    packed = np.ascontiguousarray(np.concatenate(segs).reshape(-1, 34))
+    seg = np.array([len(s) for s in segs], np.int32)
+    d_in, d_out = ctx.malloc(packed.nbytes + 8), ctx.malloc(len(packed) * 51 * 4)
+    assert d_in % 8 == 0
+    got = []
+    try:
+        for off in (0, 4):
+            ctx.h2d(d_in + off, packed)
+            ctx.h2d(d_out, np.full((len(packed), 51), np.nan, np.float32))
+            _lib.check(ctx.lib.pp_videopose3d_lift_many(net.handle, net.prog.named["input"], net.prog.named["output"], _lib.ptr(d_in + off),
+                                                        _lib.ptr(seg), len(seg), 34, 51, spec.pad, _lib.ptr(d_out), _lib.PP_MEM_DEVICE),
+                       "pp_videopose3d_lift_many")
+            ctx.synchronize()
+            got.append(np.zeros((len(packed), 51), np.float32))
+            ctx.d2h(got[-1], d_out)
+    finally:
+        ctx.free(d_in)
+        ctx.free(d_out)
+    assert np.isfinite(got[0]).all() and np.abs(got[0]).max() > 1e-4
+    assert np.array_equal(got[1], got[0])
+    net.close()
+
+
 def test_lift_many_rejects_a_bad_mem_and_a_wrong_program(ctx):
     spec = vp3d.VideoPose3DSpec(channels=CHANNELS, chunk=32)
     net = Net(ctx, vp3d.build_videopose3d_program(spec, _state_dict()), max_batch=1)
