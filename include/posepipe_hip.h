@@ -80,8 +80,9 @@ int pp_timer_start(pp_ctx* ctx);
 int pp_timer_stop(pp_ctx* ctx, float* elapsed_ms); /* synchronises on the stop event */
 /* A/B knobs of tests and profiles that select between two kernels giving IDENTICAL bits (never numerics): "decode_generic"
  * (1: the generic flip-merge / decode kernel instead of the fast one), "split_gemm_epilogue" (1: the product kernel's epilogue
- * transposed through LDS, 0: from registers).  value -1: back to the environment's choice (POSEPIPE_DECODE_GENERIC /
- * POSEPIPE_SPLIT_GEMM_EPI, read once per process).  Process-wide, thread-safe. */
+ * transposed through LDS, 0: from registers), "split_gemm_wave_tile" (1: the fp16-form product kernel's four waves 4 x 1 with wave
+ * tiles of 64 pixels x 128 channels, 0: 2 x 2 with 128 x 64).  value -1: back to the environment's choice (POSEPIPE_DECODE_GENERIC /
+ * POSEPIPE_SPLIT_GEMM_EPI / POSEPIPE_SPLIT_GEMM_TILE, read once per process).  Process-wide, thread-safe. */
 int pp_debug_knob(const char* name, int value);
 /* raw device memory helpers so that a host language without a HIP binding can keep data resident */
 int pp_malloc(pp_ctx* ctx, size_t bytes, void** dptr);

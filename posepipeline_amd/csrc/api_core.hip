@@ -7,7 +7,7 @@
 #include "pp_internal.h"
 
 #include <atomic>
-extern std::atomic<int> g_decode_generic, g_split_gemm_epi;      // dark_decode.hip, conv_split_gemm.hip
+extern std::atomic<int> g_decode_generic, g_split_gemm_epi, g_split_gemm_tile;      // dark_decode.hip, conv_split_gemm.hip (two)
 
 static thread_local std::string g_last_error;
 
@@ -70,8 +70,9 @@ int pp_debug_knob(const char* name, int value) {
     PP_REQUIRE(name && value >= -1 && value <= 1, "pp_debug_knob: name and a value in {-1, 0, 1}");
     if (!strcmp(name, "decode_generic")) g_decode_generic.store(value, std::memory_order_relaxed);
     else if (!strcmp(name, "split_gemm_epilogue")) g_split_gemm_epi.store(value, std::memory_order_relaxed);
+    else if (!strcmp(name, "split_gemm_wave_tile")) g_split_gemm_tile.store(value, std::memory_order_relaxed);
     else {
-        pp_set_error("pp_debug_knob: unknown knob '%s' (decode_generic, split_gemm_epilogue)", name);
+        pp_set_error("pp_debug_knob: unknown knob '%s' (decode_generic, split_gemm_epilogue, split_gemm_wave_tile)", name);
         return PP_ERR_ARG;
     }
     return PP_OK;

@@ -357,7 +357,7 @@ int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stre
     }
     // launch-time knobs, read once per process (the product kernel's epilogue also follows pp_debug_knob, per launch)
     static const int colmaj_mb = env_int("POSEPIPE_SPLIT_COLMAJOR_MB", 256), gemm_remap = env_int("POSEPIPE_SPLIT_GEMM_REMAP", 1);
-    static const int epi_env = env_int("POSEPIPE_SPLIT_GEMM_EPI", 1);
+    static const int epi_env = env_int("POSEPIPE_SPLIT_GEMM_EPI", 1), tile_env = env_int("POSEPIPE_SPLIT_GEMM_TILE", 1);
     static const int cob2_env = env_int("POSEPIPE_SPLIT_S2_COB", 0), cob_env = env_int("POSEPIPE_SPLIT_COB", 0);
     static const int nw8_f16 = env_int("POSEPIPE_SPLIT_NW8_F16", 0);
     static const int nw8_min_blocks = env_int("POSEPIPE_SPLIT_NW8_MIN_BLOCKS", 512), nw8_min_chunks = env_int("POSEPIPE_SPLIT_NW8_MIN_CHUNKS", 16);
@@ -422,7 +422,10 @@ int pp_launch_conv_split(const SplitPlan& p, const ConvArgs& a, hipStream_t stre
         // fp16 form: three raw float32 pixel stages of BM x 64 B + three weight stages; six-product form: two stages of split planes + weights
         const size_t lds_loop = f16 ? (size_t)3 * BM * 64 + (size_t)3 * BN * 2 * wpl * 16 : (size_t)2 * (xp * 2 * (BM + 4) * 16 + BN * 2 * wpl * 16);
         const size_t lds = std::max<size_t>(lds_loop, s.epi_lds ? (size_t)nwave * (16384 + 2048) : 0);
-        split_launch_gemm(f16, p.cin2 > 0, grid, lds, stream, s);
+        // fp16 form: 1 = the four waves 4 x 1 with 64 x 128 wave tiles (each activation converted once per workgroup), 0 = 2 x 2 with
+        // 128 x 64: two arrangements of the SAME sums (bit-identical, tests/test_gpu_split_gemm_tile.py; pp_debug_knob("split_gemm_wave_tile", ..))
+        const int tile_knob = g_split_gemm_tile.load(std::memory_order_relaxed);
+        split_launch_gemm(f16, p.cin2 > 0, (tile_knob >= 0 ? tile_knob : tile_env) != 0, grid, lds, stream, s);
         tag = "g256x128";
     } else if (p.kernel == SPLIT_S2P) {
         // strided-patch form: 128-pixel tiles, one pixel block per wave, 1 .. 4 channel blocks per wave (the widest the block count and

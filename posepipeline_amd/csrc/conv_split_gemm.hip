@@ -2,6 +2,7 @@
 #include "conv_split_internal.h"
 
 std::atomic<int> g_split_gemm_epi{-1};       // pp_debug_knob("split_gemm_epilogue"): -1 = POSEPIPE_SPLIT_GEMM_EPI
+std::atomic<int> g_split_gemm_tile{-1};      // pp_debug_knob("split_gemm_wave_tile"): -1 = POSEPIPE_SPLIT_GEMM_TILE
 
 namespace {
 
@@ -10,10 +11,20 @@ namespace {
 // vector memory path.  With the tap kernel's 256 x 64 tile that is 0.043 B/FLOP -- 10.7 TB/s at the 250 TFLOP/s the matrix pipes
 // could do, and the measured ~115 TFLOP/s of that form on ResNet's 1x1 layers is exactly ~5 TB/s of it.  A 256 x 256 tile needs
 // 0.0195 B/FLOP, which takes 128 accumulator registers per lane: 8 waves (wave tile 128 pixels x 64 channels), one workgroup per
-// CU, BOTH operands staged through LDS (X split once per workgroup and shared by the waves along N, W copied verbatim in fragment
-// order and shared by the waves along M), two LDS stages of 16 input channels, one barrier per stage (3072 matrix-pipe cycles).
+// CU, BOTH operands staged through LDS (six-product form: X split once per workgroup when it is stored to LDS and shared by the
+// waves along N; W copied verbatim in fragment order and shared by the waves along M), two LDS stages of 16 input channels, one
+// barrier per stage (3072 matrix-pipe cycles).
 // WM x WN = 8 waves: one workgroup per CU; 4 waves (256 x 128 tile): two workgroups per CU, for layers with few 16-channel stages,
-// where one workgroup's start-up and epilogue hide under the other's K loop.
+// where one workgroup's start-up and epilogue hide under the other's K loop.  Only the 4-wave form is instantiated.
+//
+// fp16 form (H): X travels to LDS as raw float32 by DMA and is split where a wave reads its fragment, so every wave that reads a
+// pixel block converts it.  WIDE: the four waves sit 4 x 1 with wave tiles of 64 pixels x 128 channels (2 pixel blocks x 4 channel
+// blocks, acc[4][2]) instead of 2 x 2 with 128 x 64 (acc[2][4]): each pixel block has ONE reader, so X is again split once per
+// workgroup -- per wave and stage 4 instead of 8 ds_read_b128 of pixels and ~48 instead of ~96 conversion instructions beside the
+// same 24 MFMAs, and 8 instead of 4 weight-fragment reads (12 fragment reads either way).  Same workgroup tile, grid, DMA rings
+// and counts; every accumulator receives the same products in the same order, so the two arrangements give the same bits
+// (tests/test_gpu_split_gemm_tile.py; measurements: DESIGN_LOG.md 5y).  WIDE is the default of the fp16 form; WIDE = false is the
+// kernel as it was (every difference is a constant of PBW / CBW or `if constexpr`).
 //
 // SEG2 (fp16 form only): a projection shortcut folded into the product.  relu(W3 h + b3 + Ws x + bs) is ONE product over the
 // concatenated K = Cin + Cin2: stages [0, seg1) stream h (a.x), stages [seg1, nchunks) stream x (a.x2, read at its own stride) into the
@@ -27,13 +38,16 @@ namespace {
 // is at most 2^-25 / s <= 2^-39 of the JOINT maximum, far under the 2^-22-relative rounding the larger segment commits on its own
 // elements, and the joint maximum is also what bounds the output.  The same holds per output channel for the weights.
 // SEG2 = false is the one-segment kernel, instruction for instruction what it was (every use of the second segment is `if constexpr`).
-template <int WM, int WN, bool H = false, bool SEG2 = false>
+template <int WM, int WN, bool H = false, bool SEG2 = false, bool WIDE = false>
 __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split_gemm_kernel(SplitArgs a) {
     static_assert(H || !SEG2, "the second K segment exists in the fp16 form only");
+    static_assert(H || !WIDE, "the 64 x 128 wave tile exists in the fp16 form only");
+    constexpr int PBW = WIDE ? 2 : 4, CBW = WIDE ? 4 : 2;      // 32-pixel x 32-channel blocks of a wave tile: 128 x 64, WIDE: 64 x 128
+    constexpr int WPX = 32 * PBW;                    // pixels of a wave
     constexpr int XP = H ? 2 : 3;                    // activation planes (H: the fp16 form, see conv_split_kernel)
     constexpr int WPL = H ? 2 : 3;                   // weight planes
     constexpr int NT = 64 * WM * WN, NWAVE = WM * WN;
-    constexpr int BM = 128 * WM, BN = 64 * WN;
+    constexpr int BM = WPX * WM, BN = 32 * CBW * WN;
     constexpr int XS = BM * 4 / NT;                  // float4 patch slots per thread and stage
     constexpr int WU = BN * 2 * WPL;                 // 16-byte units of split weights per stage: BN / 32 blocks x WPL planes x 64 lanes
     constexpr int NPp = BM + 4;
@@ -54,17 +68,18 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     (void)L; (void)col;
     const long long m0 = (long long)bx * BM;
     const int cbB = by * (BN / 32);                  // first channel block of the workgroup
-    const int cb0 = cbB + wn * 2;                    // ... of this wave
+    const int cb0 = cbB + wn * CBW;                  // ... of this wave
+    const int wp0 = wm * WPX;                        // first pixel of this wave in the tile
 
-    // sample of the wave's first / last pixel (clamped to the tensor): equal = the wave's 128 pixels lie in one sample
-    const unsigned mfirst = (unsigned)min(m0 + wm * 128, a.S - 1), mlast = (unsigned)min(m0 + wm * 128 + 127, a.S - 1);
+    // sample of the wave's first / last pixel (clamped to the tensor): equal = the wave's pixels lie in one sample
+    const unsigned mfirst = (unsigned)min(m0 + wp0, a.S - 1), mlast = (unsigned)min(m0 + wp0 + WPX - 1, a.S - 1);
     const int img_first = __builtin_amdgcn_readfirstlane((int)pp_udiv(mfirst, a.dv_per)), img_last = __builtin_amdgcn_readfirstlane((int)pp_udiv(mlast, a.dv_per));
     unsigned oam_first = 0;                          // fp16 form: maximum of that sample (the epilogue's 1 / s)
     if constexpr (H) oam_first = a.x_amax[img_first];
     if constexpr (SEG2) oam_first = max(oam_first, a.x2_amax[img_first]);       // (bit patterns of non-negative floats: integer order)
     const unsigned lds_base0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const size_t wstep0 = (size_t)a.ncb * (WPL * 64);
-    f32x16 acc[2][4];                                // (zeroed right in front of the K loops: 128 live registers less during the set-up)
+    f32x16 acc[CBW][PBW];                             // (zeroed right in front of the K loops: 128 live registers less during the set-up)
     if constexpr (H) {
     // ---- fp16 form (round 5): the pixels travel global -> LDS by DMA as well, as raw float32; the two float16 terms are made when
     // a wave reads its B fragment.  Why: with the pixels staged through registers (rounds 2 - 4, still the six-product form below) a
@@ -80,7 +95,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     // is quads 2 half and 2 half + 1 = two ds_read_b128 at the row + ((2 half) ^ swizzle) * 16 and that address ^ 16: every service
     // group of ds_read_b128 covers all 8 bank quads exactly twice (conflict-free).
     // Conversion per fragment (8 floats of one pixel): scale (power of two per sample), h0 = f16(x s), h1 = f16(x s - h0):
-    // 24 vector instructions, 96 per wave and stage beside its 24 MFMAs of 32 cycles.
+    // 24 vector instructions, 96 per wave and stage beside its 24 MFMAs of 32 cycles (WIDE: 48, two fragments instead of four).
     constexpr int XR = 3, XSTG = BM * 64, WR = 3, WBYTES = WU * 16;
     constexpr int NXD = BM / 16 / NWAVE;             // 1 KB pixel blocks (16 pixels) per wave and stage
     constexpr int NWD = WU / 64 / NWAVE;             // 1 KB weight fragments per wave and stage
@@ -105,13 +120,13 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             gx2[i] = (unsigned)(((img * a.xp2_h + ho * a.stride2) * a.xp2_w + wo * a.stride2) * a.Cin2) * 4u + (unsigned)(((lane & 3) ^ ((pl >> 1) & 3)) * 16);
         }
     }
-    float xsc[4];                                    // activation scale of the sample of pixel pb * 32 + (lane & 31)
+    float xsc[PBW];                                  // activation scale of the sample of pixel pb * 32 + (lane & 31)
 #pragma unroll
-    for (int pb = 0; pb < 4; ++pb) xsc[pb] = pp_act_scale(oam_first);
+    for (int pb = 0; pb < PBW; ++pb) xsc[pb] = pp_act_scale(oam_first);
     if (img_first != img_last) {
 #pragma unroll
-        for (int pb = 0; pb < 4; ++pb) {
-            const unsigned mp = (unsigned)min(m0 + wm * 128 + pb * 32 + (lane & 31), a.S - 1);
+        for (int pb = 0; pb < PBW; ++pb) {
+            const unsigned mp = (unsigned)min(m0 + wp0 + pb * 32 + (lane & 31), a.S - 1);
             unsigned am = a.x_amax[pp_udiv(mp, a.dv_per)];
             if constexpr (SEG2) am = max(am, a.x2_amax[pp_udiv(mp, a.dv_per)]);
             xsc[pb] = pp_act_scale(am);
@@ -142,8 +157,8 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             dma_fragment(g, xsrc, dst);
         }
     };
-    const int fofs = (wm * 128 + (lane & 31)) * 64 + ((((lane >> 5) * 2) ^ ((lane >> 1) & 3)) * 16);     // + pb * 2048; second quad: ^ 16
-    const int wofs = XR * XSTG + ((wn * 2) * (WPL * 64) + lane) * 16;                                        // + slot * WBYTES + (cb * WPL + plane) * 1024
+    const int fofs = (wp0 + (lane & 31)) * 64 + ((((lane >> 5) * 2) ^ ((lane >> 1) & 3)) * 16);     // + pb * 2048; second quad: ^ 16
+    const int wofs = XR * XSTG + ((wn * CBW) * (WPL * 64) + lane) * 16;                                      // + slot * WBYTES + (cb * WPL + plane) * 1024
     auto frag = [&](const unsigned char* sx_, int pb, uint4 (&h)[2]) {
         const float4 q0 = *reinterpret_cast<const float4*>(sx_ + (fofs + pb * 2048));
         const float4 q1 = *reinterpret_cast<const float4*>(sx_ + ((fofs + pb * 2048) ^ 16));
@@ -165,15 +180,52 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     __builtin_amdgcn_s_barrier();
     PP_TL_MARK(1);
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
+    for (int cb = 0; cb < CBW; ++cb)
 #pragma unroll
-        for (int pb = 0; pb < 4; ++pb)
+        for (int pb = 0; pb < PBW; ++pb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[cb][pb][i] = 0.f;
     for (int c = 0; c < a.nchunks; ++c) {
         const unsigned char* sxp = smem + (c % XR) * XSTG;
         const unsigned char* sw = smem + (c % WR) * WBYTES;
         uint4 wf[2][WPL], xh[2][2];
+        if constexpr (WIDE) {
+        // 64 x 128 wave tile: both pixel blocks are converted ONCE per workgroup (no other wave reads them) and stay live while the
+        // four channel blocks pass in two pairs -- every converted fragment feeds 12 MFMAs.  Per accumulator the products of a stage
+        // still arrive as g1 h0, g0 h1, g0 h0: the bits of the 128 x 64 arrangement.
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int pl = 0; pl < WPL; ++pl) wf[cb][pl] = *reinterpret_cast<const uint4*>(sw + wofs + (cb * WPL + pl) * 1024);
+        frag(sxp, 0, xh[0]);
+        if (c + 2 < a.nchunks) issue(c + 2);
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+                __builtin_amdgcn_sched_barrier(0);
+                constexpr int WI[3] = {1, 0, 0}, XI[3] = {0, 1, 0};      // g1 h0 + g0 h1 + g0 h0
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb)
+                        acc[pr * 2 + cb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[cb][WI[p]]),
+                                                                                      __builtin_bit_cast(f16x8, xh[pb][XI[p]]), acc[pr * 2 + cb][pb], 0, 0, 0);
+                    // the second pair's weight fragments: plane 1 (what its first MFMAs read) as soon as this pair's last reader of
+                    // that plane is issued, plane 0 behind the last MFMA -- it lands under the next block's first two
+                    if (pr == 0 && pb == 1 && p != 1) {
+                        if (p == 0) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int cb = 0; cb < 2; ++cb)
+                            wf[cb][p == 0 ? 1 : 0] = *reinterpret_cast<const uint4*>(sw + wofs + ((2 + cb) * WPL + (p == 0 ? 1 : 0)) * 1024);
+                        if (p == 0) __builtin_amdgcn_sched_barrier(0);      // (else the scheduler sinks these reads to the end of the block)
+                    }
+                }
+                // the second pixel block is read and converted in the shadow of the first block's MFMAs
+                if (pr == 0 && pb == 0) frag(sxp, 1, xh[1]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -195,6 +247,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             if (pb < 3) frag(sxp, pb + 1, xh[(pb + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
         }
+        }   // !WIDE
         // stage c + 1 has landed (younger in the queue: only what this stage requested for c + 2); every LDS read of this stage is done
         if (c + 2 < a.nchunks) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NXD + NWD) : "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -273,9 +326,9 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     PP_TL_MARK(1);
 
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
+    for (int cb = 0; cb < CBW; ++cb)
 #pragma unroll
-        for (int pb = 0; pb < 4; ++pb)
+        for (int pb = 0; pb < PBW; ++pb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[cb][pb][i] = 0.f;
     for (int c = 0; c < a.nchunks; ++c) {
@@ -335,17 +388,18 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     // ---- epilogue, transposed through LDS (a.epi_lds) ----------------------------------------------------------------------------
     // A lane holds 4 consecutive channels of ONE pixel (lane & 31): stored from the registers, an instruction touches 32 pixels with
     // 32 bytes each.  The stages are free here (every wave passed the loop's last barrier after its last fragment read), so each
-    // wave transposes its 128 pixels x 32 channels (one channel block at a time) through 16 KiB of its own ([128][128 B], 16-byte
-    // chunk ^ (pixel & 7)) and stores whole 128-byte lines, 8 pixels per instruction; residuals are read in the same lines.  The
-    // pixel -> (output, residual) offsets are computed once per pixel (two lanes' worth of divisions per wave, not per store) into
-    // a 2 KiB table beside it.  Same arithmetic per element, in the same order, as the register epilogue below: identical bits.
+    // wave transposes its WPX pixels x 32 channels (one channel block at a time) through a region of its own ([WPX][128 B]: 16 KiB
+    // of 128 pixels, WIDE: 8 KiB of 64; 16-byte chunk ^ (pixel & 7)) and stores whole 128-byte lines, 8 pixels per instruction;
+    // residuals are read in the same lines.  The pixel -> (output, residual) offsets are computed once per pixel (one or two lanes'
+    // worth of divisions per wave, not per store) into a table behind it (16 B per pixel).  Same arithmetic per element, in the same
+    // order, as the register epilogue below: identical bits.
     if (a.epi_lds) {
         unsigned char* stg = smem + wave * (16384 + 2048);
         uint4* tab = reinterpret_cast<uint4*>(stg + 16384);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < WPX / 64; ++i) {
             const int p = lane + 64 * i;
-            const long long m = m0 + wm * 128 + p;
+            const long long m = m0 + wp0 + p;
             uint4 t = make_uint4(0u, 0u, 0u, 0u);
             if (m < a.S) {
                 const int img = (int)pp_udiv((unsigned)m, a.dv_per), rem = (int)((unsigned)m - (unsigned)img * (unsigned)(a.H * a.W));
@@ -359,14 +413,14 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             tab[p] = t;
         }
         const int rdrow = lane >> 3, rdpos = lane & 7, rdchunk = rdpos ^ rdrow;
-        float xinv[H ? 4 : 1];                       // H: 1 / s of the sample of pixel pb * 32 + (lane & 31)
+        float xinv[H ? PBW : 1];                     // H: 1 / s of the sample of pixel pb * 32 + (lane & 31)
         if constexpr (H) {
 #pragma unroll
-            for (int pb = 0; pb < 4; ++pb) xinv[pb] = pp_act_unscale(oam_first);
+            for (int pb = 0; pb < PBW; ++pb) xinv[pb] = pp_act_unscale(oam_first);
             if (img_first != img_last) {
 #pragma unroll
-                for (int pb = 0; pb < 4; ++pb) {
-                    const unsigned mp = (unsigned)min(m0 + wm * 128 + pb * 32 + (lane & 31), a.S - 1);
+                for (int pb = 0; pb < PBW; ++pb) {
+                    const unsigned mp = (unsigned)min(m0 + wp0 + pb * 32 + (lane & 31), a.S - 1);
                     unsigned am = a.x_amax[pp_udiv(mp, a.dv_per)];
                     if constexpr (SEG2) am = max(am, a.x2_amax[pp_udiv(mp, a.dv_per)]);
                     xinv[pb] = pp_act_unscale(am);
@@ -375,9 +429,9 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
         }
         float ymax = 0.f, ymax1 = 0.f;               // max |y| of the lane's pixels in img_first / (two samples in the wave) in img_last
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
+        for (int cb = 0; cb < CBW; ++cb) {
 #pragma unroll
-            for (int pb = 0; pb < 4; ++pb)
+            for (int pb = 0; pb < PBW; ++pb)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int co = (cb0 + cb) * 32 + 8 * g + 4 * (lane >> 5);
@@ -389,7 +443,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
                     epi_value<H>(v, cc[4 * g + 0], cc[4 * g + 1], cc[4 * g + 2], cc[4 * g + 3], b4, sc, xinv[H ? pb : 0], a.relu, false, NO_R2);
                     *reinterpret_cast<float4*>(stg + (pb * 32 + (lane & 31)) * 128 + (((2 * g + (lane >> 5)) ^ (lane & 7)) << 4)) = v;
                 }
-            // the 16 residual lines of this channel block are requested back to back (from clamped, always valid addresses) before
+            // the residual lines of this channel block (16, WIDE: 8) are requested back to back (from clamped, always valid addresses) before
             // any of them is consumed: ONE memory round trip per residual and channel block instead of sixteen in a row -- round
             // 4's timeline put the epilogue of the residual layers (256 -> 1024 at 40x68) at the length of their K loop
             const int co = (cb0 + cb) * 32 + rdchunk * 4;
@@ -397,7 +451,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
             // two batches of eight lines (round 5): with all sixteen in flight (64 + 64 registers beside the 64 accumulator registers of
             // the other channel block) the allocator spilled accumulator tuples -- and kept them spilled INSIDE the K loop
 #pragma unroll
-            for (int h8 = 0; h8 < 2; ++h8) {
+            for (int h8 = 0; h8 < WPX / 64; ++h8) {
             float4 vv[8];
 #pragma unroll
             for (int i8 = 0; i8 < 8; ++i8) vv[i8] = *reinterpret_cast<const float4*>(stg + ((h8 * 8 + i8) * 8 + rdrow) * 128 + rdpos * 16);
@@ -455,11 +509,11 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     }
 
     // ---- epilogue (as conv_split_kernel) -----------------------------------------------------------------------------------------
-    int rimg[4];
-    float rmax[4];
+    int rimg[PBW];
+    float rmax[PBW];
 #pragma unroll
-    for (int pb = 0; pb < 4; ++pb) {
-        const long long mt = m0 + wm * 128 + pb * 32 + (lane & 31);
+    for (int pb = 0; pb < PBW; ++pb) {
+        const long long mt = m0 + wp0 + pb * 32 + (lane & 31);
         const bool pok = mt < a.S;
         const long long m = pok ? mt : a.S - 1;
         const int img = (int)pp_udiv((unsigned)m, a.dv_per), rem = (int)((unsigned)m - (unsigned)img * (unsigned)(a.H * a.W));
@@ -472,7 +526,7 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
         const size_t r1pix = ((size_t)img * (a.r1_H + a.r1_pad) + (oy >> a.r1_shift)) * (a.r1_W + a.r1_pad) + (ox >> a.r1_shift);
         const size_t r2pix = ((size_t)img * (a.H + a.r2_pad) + oy) * (a.W + a.r2_pad) + ox;
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
+        for (int cb = 0; cb < CBW; ++cb) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int co = (cb0 + cb) * 32 + 8 * g + 4 * (lane >> 5);
@@ -506,16 +560,20 @@ __global__ __launch_bounds__(64 * WM * WN, 512 / (64 * WM * WN)) void conv_split
     }
     if (a.y_amax) {
         const unsigned wlast = (unsigned)min(m0 + BM - 1, a.S - 1);
-        pp_amax_commit_wg<NWAVE, 4>(a.y_amax, rimg, rmax, (int)pp_udiv((unsigned)min(m0, (long long)wlast), a.dv_per), (int)pp_udiv(wlast, a.dv_per),
+        pp_amax_commit_wg<NWAVE, PBW>(a.y_amax, rimg, rmax, (int)pp_udiv((unsigned)min(m0, (long long)wlast), a.dv_per), (int)pp_udiv(wlast, a.dv_per),
                                     reinterpret_cast<float*>(smem));
     }
 }
 
 }  // namespace
 
-// 256 x 128 tiles, 4 waves; seg2: with a folded shortcut as the second K segment (fp16 form)
-void split_launch_gemm(bool f16, bool seg2, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s) {
-    if (seg2) launch_split<conv_split_gemm_kernel<2, 2, true, true>, 80 * 1024>(grid, 256, lds, stream, s);
+// 256 x 128 tiles, 4 waves; seg2: with a folded shortcut as the second K segment (fp16 form); fp16 form: the waves 4 x 1 with 64 x 128
+// wave tiles (wide), or 2 x 2 with 128 x 64: the same bits (pp_debug_knob("split_gemm_wave_tile", ..), read by the caller)
+void split_launch_gemm(bool f16, bool seg2, bool wide, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s) {
+    wide = wide && f16;
+    if (seg2 && wide) launch_split<conv_split_gemm_kernel<4, 1, true, true, true>, 80 * 1024>(grid, 256, lds, stream, s);
+    else if (wide) launch_split<conv_split_gemm_kernel<4, 1, true, false, true>, 80 * 1024>(grid, 256, lds, stream, s);
+    else if (seg2) launch_split<conv_split_gemm_kernel<2, 2, true, true>, 80 * 1024>(grid, 256, lds, stream, s);
     else if (f16) launch_split<conv_split_gemm_kernel<2, 2, true>, 80 * 1024>(grid, 256, lds, stream, s);
     else launch_split<conv_split_gemm_kernel<2, 2, false>, 80 * 1024>(grid, 256, lds, stream, s);
 }

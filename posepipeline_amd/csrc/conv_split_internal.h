@@ -13,7 +13,7 @@ constexpr int STEM_SLOTS = (STEM_PH * STEM_PW + 511) / 512;
 constexpr int STEM_LDS = STEM_WBYTES + 2 * STEM_BUF + 256;
 
 void pp_split_make_magic(unsigned d, unsigned (&dv)[2]);      // conv_split.hip
-extern std::atomic<int> g_split_gemm_epi;            // conv_split_gemm.hip
+extern std::atomic<int> g_split_gemm_epi, g_split_gemm_tile;      // conv_split_gemm.hip
 
 // launches kernel K with `lds` bytes of dynamic LDS; more than 64 KB has to be allowed per kernel, once per device (up to MAX_LDS)
 template <auto K, int MAX_LDS, class Args>
@@ -48,5 +48,5 @@ void split_launch_tap_gemm(int cob, bool f16, dim3 grid, size_t lds, hipStream_t
 void split_launch_tap_nw8(int nslot, int cob, bool f16, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s);     // conv_split_tap_nw8.hip
 void split_launch_tap_s2p(int nslot, int cob, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s);               // conv_split_weights.hip
 void split_launch_c48(int nslot, bool f16, bool ring, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s);       // conv_split_c48.hip
-void split_launch_gemm(bool f16, bool seg2, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s);                 // conv_split_gemm.hip
+void split_launch_gemm(bool f16, bool seg2, bool wide, dim3 grid, size_t lds, hipStream_t stream, const SplitArgs& s);                 // conv_split_gemm.hip
 int split_launch_stem7(const ConvArgs& a, hipStream_t stream);                                                                    // conv_split_stem.hip
